@@ -113,3 +113,73 @@ def sample(case, name, t):
 
 def path(case):
     return os.path.join(GOLDEN_DIR, case + ".npz")
+
+
+# ---- reference pins (tests/golden/make_reference_pins.py): what the CPU tests used to read from a live reference tree ----
+
+PINS_JSON = os.path.join(GOLDEN_DIR, "reference_pins.json")
+PINS_NPZ = os.path.join(GOLDEN_DIR, "reference_pins.npz")
+
+
+def digest(a):
+    """sha256 of an array's dtype, shape and bytes: a bit-exact comparison stored in 64 hex digits."""
+    import hashlib
+    import numpy as np
+    a = np.ascontiguousarray(a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a))
+    h = hashlib.sha256(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def signature_rows(fn):
+    """[name, kind, repr(default)] per parameter of inspect.signature(fn)."""
+    import inspect
+    return [[p.name, str(p.kind), repr(p.default)] for p in inspect.signature(fn).parameters.values()]
+
+
+class Pin(object):
+    """A pinned reference array: its shape, the largest |value| of the whole array and a strided sample of its
+    flattened elements (every `stride`-th, from 0)."""
+
+    def __init__(self, values, stride, shape, absmax):
+        self.values, self.stride, self.shape, self.absmax = values, stride, tuple(shape), absmax
+
+    def sample(self, t):
+        """The same positions of an array of this shape."""
+        import numpy as np
+        a = t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+        assert tuple(a.shape) == self.shape, (tuple(a.shape), self.shape)
+        return a.reshape(-1)[::self.stride]
+
+
+def pin_error(got, pin):
+    """Largest |got - reference| over the pinned positions (got: the full array, of the pinned shape)."""
+    import numpy as np
+    return float(np.abs(pin.sample(got).astype(np.float64) - pin.values.astype(np.float64)).max())
+
+
+def pack_pins(arrays, cap):
+    """{key: float array} -> (index for the JSON, one float32 array): at most cap(key) elements of each array."""
+    import numpy as np
+    index, parts, offset = {}, [], 0
+    for key in sorted(arrays):
+        a = np.asarray(arrays[key], dtype=np.float32)
+        stride = max(1, -(-a.size // cap(key)))
+        v = a.reshape(-1)[::stride]
+        index[key] = {"shape": list(a.shape), "stride": stride, "offset": offset, "size": int(v.size),
+                      "absmax": float(np.abs(a).max()) if a.size else 0.0}
+        parts.append(v)
+        offset += v.size
+    return index, np.concatenate(parts)
+
+
+def load_pins():
+    """(the JSON pins, {key: Pin})."""
+    import json
+    import numpy as np
+    pins = json.load(open(PINS_JSON))
+    with np.load(PINS_NPZ) as z:
+        values = z["values"]
+    arrays = {k: Pin(values[e["offset"]:e["offset"] + e["size"]], e["stride"], e["shape"], e["absmax"])
+              for k, e in pins["arrays"].items()}
+    return pins, arrays

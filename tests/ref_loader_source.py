@@ -7,7 +7,7 @@ import os
 import numpy as np
 import torch
 
-REF = "/root/reference"
+from oracle.ref_loader import REFERENCE_ROOT as REF  # (VILBERT_REFERENCE_ROOT, as for the model)
 
 
 def available():

@@ -57,3 +57,55 @@ def test_bench_starts_its_own_ranks_when_not_under_a_launcher():
     assert r.returncode != 0
     text = r.stdout + r.stderr
     assert "GPU(s) visible" in text, text[-2000:]
+
+
+def test_dump_outputs_writes_float32_within_budget_and_samples_repeatably(tmp_path):
+    """--dump-outputs: float32 files (float64 kept), arrays over their share of the budget replaced by the same seeded
+    sample on every call, all files together under 64 MB."""
+    import numpy as np
+    g = torch.Generator().manual_seed(0)
+    arrays = {"small": torch.randn(3, 5, generator=g), "wide": torch.randn(9000, 4000, generator=g),
+              "half": torch.randn(7, generator=g).to(torch.bfloat16), "exact": torch.randn(4, dtype=torch.float64, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in arrays}
+    assert got["small"].dtype == np.float32 and np.array_equal(got["small"], arrays["small"].numpy())
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], arrays["half"].float().numpy())
+    assert got["exact"].dtype == np.float64 and np.array_equal(got["exact"], arrays["exact"].numpy())
+    assert got["wide"].dtype == np.float32 and got["wide"].ndim == 1 and 0 < got["wide"].size < 9000 * 4000
+    assert np.isin(got["wide"], arrays["wide"].numpy()).all()
+    assert np.array_equal(got["wide"], np.load(str(tmp_path / "b" / "wide.npy")))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+
+
+def test_parameter_samples_follow_named_parameters():
+    net = torch.nn.Sequential(torch.nn.Linear(300, 200), torch.nn.Linear(200, 2))
+    net[0].weight.grad = torch.ones_like(net[0].weight)
+    vals, grads = bench.parameter_samples(net, per_param=64)
+    assert vals.shape == grads.shape == (64 + 64 + 64 + 2,)
+    assert (grads[:64] == 1).all() and (grads[64:] == 0).all()
+    assert torch.equal(vals, bench.parameter_samples(net, per_param=64)[0])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps, prints the headline keys and none of the --full legs, and --dump-outputs
+    leaves the last step's losses and the parameter / gradient samples as float32 .npy files."""
+    import json
+    import subprocess
+    import numpy as np
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "16", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["unit"] == "samples/s" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(16 * 1e3 / line["ms_per_step"], rel=1e-2)
+    assert not {"roofline", "alt_gemm_modes", "cpu_baseline", "b64", "fwd_b512", "summary"} & set(line)
+    names = {"masked_lm_loss", "masked_img_loss", "next_sentence_loss", "parameters_after_step_sample", "gradients_sample"}
+    assert {p.stem for p in tmp_path.iterdir()} == names
+    for n in names:
+        a = np.load(str(tmp_path / (n + ".npy")))
+        assert a.dtype == np.float32 and np.isfinite(a).all(), n
+    assert np.abs(np.load(str(tmp_path / "gradients_sample.npy"))).max() > 0

@@ -1,5 +1,6 @@
 """Row f3: device-side finishing of a pre-training batch.
-CPU: the oracle (oracle/batch_oracle.py) against the reference's own code and the golden fixture.
+CPU: the oracle (oracle/batch_oracle.py) against the reference's own code (its outputs recorded in
+tests/golden/reference_pins.json) and the golden fixture.
 GPU: vb_concap_finish_batch / DeviceBatchPipeline against the oracle - bit-exact (integer, copy and
 correctly-rounded fp32 work)."""
 import os
@@ -8,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-import ref_loader_source as rls
+from helpers import cases
 from oracle import batch_oracle as bo
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "concap_batch.npz")
@@ -39,21 +40,20 @@ def test_oracle_matches_golden_reference_outputs():
     assert (raw["masked_label"] == 0).sum(1).min() == 0                        # and the divisor clamp
 
 
-@pytest.mark.skipif(not rls.available(), reason="needs /root/reference (build container only)")
 @pytest.mark.parametrize("seed,shape", [(3, dict(batch=5, tokens=12, regions=9, feat_dim=32, n_classes=7)),
                                         (4, dict(batch=3, tokens=36, regions=36, feat_dim=2048, n_classes=1601))])
 def test_oracle_matches_the_reference_code_run_live(seed, shape):
+    """Bit-exact: sha256 of dtype, shape and bytes of every output against the reference loader's
+    (ConceptCapLoaderTrain.__iter__ + the objective-1 edit of train_concap.py, run by tests/golden/make_reference_pins.py)."""
+    want = cases.load_pins()[0]["batch_finishing"][str(seed)]
     raw = bo.make_raw_batch(seed=seed, **shape)
-    tup = tuple(raw[n].copy() for n in bo.RAW_FIELDS) + (np.arange(shape["batch"]),)
-    got = rls.reference_loader_iter([tup])[0]
     out = bo.finish_batch(raw, objective=0)
+    assert len(want["objective0"]) == len(bo.OUT_FIELDS)
     for i, n in enumerate(bo.OUT_FIELDS):
-        _same(out[n], got[i].numpy(), n)
-    il1, lm1 = rls.reference_objective1_edit(torch.tensor(raw["image_label"]), torch.tensor(raw["lm_label_ids"]),
-                                             torch.tensor(raw["is_next"]))
+        assert cases.digest(out[n]) == want["objective0"][i], n
     out1 = bo.finish_batch(raw, objective=1)
-    _same(out1["image_label"], il1.numpy(), "image_label")
-    _same(out1["lm_label_ids"], lm1.numpy(), "lm_label_ids")
+    assert cases.digest(out1["image_label"]) == want["image_label"]
+    assert cases.digest(out1["lm_label_ids"]) == want["lm_label_ids"]
 
 
 def _to_dev(raw):

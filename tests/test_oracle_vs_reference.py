@@ -1,37 +1,29 @@
-"""Pins oracle/ (restatement + parameter table) against the REAL reference model.
+"""Pins oracle/ (restatement + parameter table) against the REAL reference model: the state_dict table, the tiny
+model's forward outputs and the pre-training losses and gradients.
 
-Runs only where /root/reference exists (the build container); on the GPU box the committed
-fixtures in tests/golden/ (made from the same reference by tests/golden/make_golden.py) pin it.
-"""
+Everywhere: against values recorded from the reference (tests/golden/reference_pins.{json,npz}, written by
+tests/golden/make_reference_pins.py - float arrays as strided samples with the whole array's shape and largest
+|value|, so the tolerances are the same). Where the reference tree is present: also against every element the
+reference itself computes."""
 import pytest
 import torch
 
+from helpers import cases
 from oracle import ref_loader, synth, vilbert_oracle as vo
 
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
+import make_reference_pins as mrp
 
 
-def _ref_model(cfg, kind, sd):
-    ref = ref_loader.load()
-    rc = ref.BertConfig.from_dict(cfg)
-    m = ref.BertForMultiModalPreTraining(rc) if kind == "pretraining" else ref.VILBertForVLTasks(rc, num_labels=1)
-    missing = m.load_state_dict(sd, strict=True)
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return m.eval()
+@pytest.fixture(scope="module")
+def pins():
+    return cases.load_pins()
 
 
 @pytest.mark.parametrize("kind", ["pretraining", "vltasks"])
 @pytest.mark.parametrize("cfgname", ["tiny", "tiny_task", "bert_base_2layer_2conect.json"])
-def test_param_table_matches_reference_state_dict(kind, cfgname):
-    ref = ref_loader.load()
-    cfg = (synth.tiny_config() if cfgname == "tiny" else synth.tiny_config(task_specific_tokens=True)
-           if cfgname == "tiny_task" else synth.load_config(cfgname))
-    if cfgname.endswith(".json"):
-        cfg = dict(cfg, num_hidden_layers=2, t_biattention_id=[0, 1])  # keep the ctor cheap
-    rc = ref.BertConfig.from_dict(cfg)
-    m = ref.BertForMultiModalPreTraining(rc) if kind == "pretraining" else ref.VILBertForVLTasks(rc, 1)
-    want = [(k, tuple(v.shape)) for k, v in m.state_dict().items()]
-    got = [(n, tuple(s)) for n, s, _ in synth.param_table(cfg, kind)]
+def test_param_table_matches_reference_state_dict(kind, cfgname, pins):
+    want = [(k, tuple(s)) for k, s in pins[0]["state_dict"]["%s/%s" % (kind, cfgname)]]
+    got = [(n, tuple(s)) for n, s, _ in synth.param_table(mrp.state_dict_cfg(cfgname), kind)]
     assert got == want
 
 
@@ -41,57 +33,57 @@ def _close(a, b, tol):
     assert err <= tol, err
 
 
-def test_vltasks_forward_matches_reference():
-    cfg = synth.tiny_config()
-    sd = synth.make_state_dict(cfg, "vltasks")
-    x = synth.make_inputs(cfg, 4, 9, 7)
-    args = (x["input_ids"], x["image_feat"], x["image_loc"], x["token_type_ids"], x["attention_mask"],
-            x["image_attention_mask"], x["co_attention_mask"])
-    with torch.no_grad():
-        want = _ref_model(cfg, "vltasks", sd)(*args)[:9]
-        got = vo.vltasks_forward(sd, cfg, *args)
-    for g, w in zip(got, want):
-        _close(g, w, 2e-6 * max(1.0, w.abs().max().item()))
+def _pinned_close(a, pin, tol):
+    err = cases.pin_error(a, pin)
+    assert err <= tol, err
 
 
-def test_task_tokens_and_odd_batch():
-    cfg = synth.tiny_config(task_specific_tokens=True)
-    sd = synth.make_state_dict(cfg, "vltasks")
-    x = synth.make_inputs(cfg, 3, 6, 5, task_id=4)
-    args = (x["input_ids"], x["image_feat"], x["image_loc"], x["token_type_ids"], x["attention_mask"],
-            x["image_attention_mask"], x["co_attention_mask"], x["task_ids"])
+def _forward_matches(tag, case, arrays):
+    cfg, sd, args = case
     with torch.no_grad():
-        want = _ref_model(cfg, "vltasks", sd)(*args)[:9]
         got = vo.vltasks_forward(sd, cfg, *args)
-    for g, w in zip(got, want):
-        _close(g, w, 2e-6 * max(1.0, w.abs().max().item()))
+    for i, g in enumerate(got[:9]):
+        pin = arrays["%s/%d" % (tag, i)]
+        _pinned_close(g, pin, 2e-6 * max(1.0, pin.absmax))
+    if ref_loader.available():
+        for g, w in zip(got, mrp.reference_vltasks(cfg, sd, args)):
+            _close(g, w, 2e-6 * max(1.0, w.abs().max().item()))
+
+
+def test_vltasks_forward_matches_reference(pins):
+    _forward_matches("vltasks_forward", mrp.vltasks_case(), pins[1])
+
+
+def test_task_tokens_and_odd_batch(pins):
+    _forward_matches("task_tokens", mrp.task_tokens_case(), pins[1])
 
 
 @pytest.mark.parametrize("visual_target", [0, 1])
-def test_pretraining_losses_and_grads_match_reference(visual_target):
-    cfg = synth.tiny_config(visual_target=visual_target, hidden_dropout_prob=0.0,
-                            attention_probs_dropout_prob=0.0, v_hidden_dropout_prob=0.0,
-                            v_attention_probs_dropout_prob=0.0)
-    sd = synth.make_state_dict(cfg, "pretraining")
-    x = synth.make_inputs(cfg, 4, 9, 8, with_labels=True)
-    if visual_target == 1:
-        x["image_target"] = torch.randn(4, 7, cfg["v_target_size"])
-    args = (x["input_ids"], x["image_feat"], x["image_loc"], x["token_type_ids"], x["attention_mask"],
-            x["image_attention_mask"], x["masked_lm_labels"], x["image_label"], x["image_target"],
-            x["next_sentence_label"])
-    m = _ref_model(cfg, "pretraining", sd)
-    m.cls.dropout.p = 0.0
-    m.train()
-    ref_losses = m(*args)
-    sum(l.sum() for l in ref_losses).backward()
+def test_pretraining_losses_and_grads_match_reference(visual_target, pins):
+    cfg, sd, args = mrp.pretraining_case(visual_target)
+    arrays = pins[1]
     leaves = {k: v.clone().requires_grad_(True) for k, v in sd.items() if not k.endswith("decoder.weight") or "image" in k}
     leaves["cls.predictions.decoder.weight"] = leaves["bert.embeddings.word_embeddings.weight"]
     got = vo.pretraining_forward(leaves, cfg, *args)
     sum(l.sum() for l in got).backward()
-    for g, w in zip(got, ref_losses):
-        _close(g.detach(), w.detach(), 1e-5)
-    for name, p in m.named_parameters():
-        if p.grad is None:
-            assert leaves[name].grad is None or leaves[name].grad.abs().max() == 0, name
-        else:
-            _close(leaves[name].grad, p.grad, 1e-5 * max(1.0, p.grad.abs().max().item()))
+    for i, g in enumerate(got):
+        _pinned_close(g.detach(), arrays["pretraining_vt%d/loss/%d" % (visual_target, i)], 1e-5)
+    prefix = "pretraining_vt%d/grad/" % visual_target
+    no_grad = pins[0]["pretraining_vt%d_no_grad" % visual_target]
+    for name in no_grad:
+        assert leaves[name].grad is None or leaves[name].grad.abs().max() == 0, name
+    n = 0
+    for key, pin in arrays.items():
+        if key.startswith(prefix):
+            _pinned_close(leaves[key[len(prefix):]].grad, pin, 1e-5 * max(1.0, pin.absmax))
+            n += 1
+    assert n > 0
+    if ref_loader.available():
+        want_losses, want_grads = mrp.reference_pretraining(cfg, sd, args)
+        for g, w in zip(got, want_losses):
+            _close(g.detach(), w, 1e-5)
+        for name, w in want_grads.items():
+            if w is None:
+                assert leaves[name].grad is None or leaves[name].grad.abs().max() == 0, name
+            else:
+                _close(leaves[name].grad, w, 1e-5 * max(1.0, w.abs().max().item()))

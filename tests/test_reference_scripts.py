@@ -12,6 +12,7 @@ import sys
 import pytest
 import torch
 
+from helpers import cases
 from oracle import ref_loader, task_forward_oracle as tf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -167,7 +168,7 @@ def test_without_a_reference_checkout_the_package_stands_alone():
     assert "VILBERT_REFERENCE_ROOT" in p.stdout
 
 
-def test_compat_placeholders():
+def test_compat_placeholders(tmp_path):
     sys.path.insert(0, PKG)
     from vilbert import _compat
     made = _compat.install()
@@ -187,7 +188,7 @@ def test_compat_placeholders():
             lmdb.open("/nonexistent")
     if "jsonlines" in made:
         import jsonlines
-        p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "vb_compat_test.jsonl")
+        p = str(tmp_path / "vb_compat_test.jsonl")
         with open(p, "w") as f:
             f.write('{"a": 1}\n\n{"a": 2}\n')
         with jsonlines.open(p) as r:
@@ -212,46 +213,36 @@ class _CannedModel(object):
                 r_(n, t, 30522 // 64), r_(n, t, 1), None)
 
 
-@needs_reference
+class _Loader(list):
+    """A one-batch loader whose iterator also has the torch-0.4 `.next()` (task_utils.py:186 calls it)."""
+
+    def __iter__(self):
+        it = super().__iter__()
+
+        class _It(object):
+            def __iter__(self_):
+                return self_
+
+            def __next__(self_):
+                return next(it)
+            next = __next__
+        return _It()
+
+
 @pytest.mark.parametrize("task_id", sorted(tf.TASKS))
-def test_task_forward_restatement_matches_reference(task_id, monkeypatch):
+def test_task_forward_restatement_matches_reference(task_id):
     """oracle/task_forward_oracle.py vs the reference's own ForwardModelsTrain on the same batch and stand-in model:
-    identical model arguments, loss and score for every (type, process) pair."""
-    sys.path.insert(0, PKG)
-    import vilbert
-    vilbert.attach_reference(ref_loader.REFERENCE_ROOT)
-    from vilbert import _compat
-    _compat.install()
-    if ref_loader.REFERENCE_ROOT not in sys.path:
-        sys.path.append(ref_loader.REFERENCE_ROOT)
-    import vilbert.task_utils as TU
-    import yaml
-    monkeypatch.setattr(torch.Tensor, "cuda", lambda self, *a, **k: self)
-    task_cfg = yaml.safe_load(open(os.path.join(ref_loader.REFERENCE_ROOT, "vilbert_tasks.yml")))
-    kind, loss_name, process = tf.TASKS[task_id]
-    assert (task_cfg[task_id]["type"], task_cfg[task_id]["loss"], task_cfg[task_id]["process"]) == (kind, loss_name, process)
+    identical model arguments, loss and score for every (type, process) pair. The reference side is pinned in
+    tests/golden/reference_pins.json (sha256 of dtype, shape and bytes; tests/golden/make_reference_pins.py)."""
+    pins, _ = cases.load_pins()
+    want = pins["forward_models_train"][task_id]
+    assert list(tf.TASKS[task_id]) == want["type_loss_process"]
+    kind = tf.TASKS[task_id][0]
     n_reg = 110 if kind == "V-logit-mc" else 9
     batch = tf.make_task_batch(task_id, 4, 7, n_reg, seed=5)
-
-    class _Loader(list):
-        def __iter__(self):
-            it = super().__iter__()
-
-            class _It(object):
-                def __iter__(self_):
-                    return self_
-
-                def __next__(self_):
-                    return next(it)
-                next = __next__                      # torch-0.4 loader iterators had .next(), which task_utils.py:186 calls
-            return _It()
-    ref_model, our_model = _CannedModel(3129, 3), _CannedModel(3129, 3)
-    losses = TU.LoadLosses(None, task_cfg, [task_id[4:]])
-    want_loss, want_score = TU.ForwardModelsTrain(None, task_cfg, "cpu", task_id, {task_id: 0}, {task_id: None},
-                                                  {task_id: _Loader([batch])}, ref_model, losses)
+    our_model = _CannedModel(3129, 3)
     got_loss, got_score = tf.forward_train(task_id, batch, our_model)
-    assert len(ref_model.calls) == len(our_model.calls) == 1
-    for a, b in zip(ref_model.calls[0], our_model.calls[0]):
-        assert a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
-    assert torch.equal(want_loss, got_loss)
-    assert float(want_score) == float(got_score)
+    assert len(our_model.calls) == want["calls"] == 1
+    assert [cases.digest(t) for t in our_model.calls[0]] == want["model_args"]
+    assert cases.digest(got_loss.detach()) == want["loss"]
+    assert float(got_score) == want["score"]
