@@ -94,7 +94,8 @@ int vb_set_gemm_tile(int code);
  * that finds no free slice (a ninth stream) or whose partials do not fit falls back to the atomics for that launch -
  * never an error - and is counted by vb_deterministic_fallbacks(). Registering the same buffer again keeps the
  * stream -> slice assignment; on = 0 drops every device's registration. The embedding-table gradients
- * (vb_text_embed_bwd) still use atomics. Returns the previous setting (0 / 1) or a negative error. */
+ * (vb_text_embed_bwd) follow the same setting: ordered keyed reduction in the stream's slice, atomics (counted) when the
+ * slice is missing or too small. Returns the previous setting (0 / 1) or a negative error. */
 int vb_set_deterministic(int on, void* workspace, int64_t workspace_bytes);
 /* Split launches since the last vb_set_deterministic(1, ...) that wanted the ordered reduce and ran with atomics. */
 int64_t vb_deterministic_fallbacks(void);
@@ -387,10 +388,21 @@ int vb_text_embed_ln_fwd(void* stream, int32_t batch, int32_t n_tok, int32_t hid
                          const float* gamma, const float* beta, float eps, float* out,
                          float* mean, float* rstd, float* presum);
 
-/* vb_text_embed_bwd: scatter-add (fp32 atomics) of dx [batch, n_tok (+1), hidden] - the gradient of
- * the pre-LayerNorm sum - into the ZERO-FILLED (or accumulating) tables dword / dpos / dtype / dtask.
+/* vb_text_embed_bwd: scatter-add of dx [batch, n_tok (+1), hidden] - the gradient of the pre-LayerNorm
+ * sum - into the ZERO-FILLED (or accumulating) tables dword / dpos / dtype / dtask.
  * Word row 0 is nn.Embedding's padding_idx (vilbert.py:330-332) and receives nothing; ids outside
- * [0, vocab) / [0, n_types) / [0, n_tasks) are skipped (dtype holds n_types rows - possibly one). */
+ * [0, vocab) / [0, n_types) / [0, n_tasks) are skipped (dtype holds n_types rows - possibly one); the
+ * task-token row (t_out = 1 when task_ids != NULL) has no position and no type.
+ * Deterministic setting off (vb_set_deterministic): fp32 atomics, the order of the adds is the order the
+ * blocks run in. Setting on (the default): the result depends on the inputs alone. Every table is a keyed
+ * reduction over the rows r = b * n_out + t_out of dx (key = word id / position / type / task id): a key's
+ * rows are visited in ascending r and cut into consecutive runs of R = 64 rows (EMB_RUN, csrc/embed_bwd.hip);
+ * each run is summed left to right in fp32, the run sums are added left to right, and the total goes into
+ * the table row with one add (row = row + total: a tied decoder gradient or an accumulated micro-batch
+ * already in the row stays deterministic too). Scratch is the calling stream's slice of the deterministic
+ * workspace (no allocation, no memset, no host sync: capture-safe); without a slice, or when it is too
+ * small (or vocab + n_tok + n_types + n_tasks >= 2^18), the atomics run and vb_deterministic_fallbacks()
+ * counts the call. */
 int vb_text_embed_bwd(void* stream, int32_t batch, int32_t n_tok, int32_t hidden, int32_t vocab,
                       int32_t n_types, int32_t n_tasks, const int64_t* ids, const int64_t* seg,
                       const int64_t* task_ids, const float* dx, float* dword, float* dpos, float* dtype,

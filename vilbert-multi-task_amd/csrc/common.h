@@ -17,6 +17,15 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // device pointer registered with vb_set_seed_epoch (or null): every dropout launch passes it to its kernel
 const uint64_t* vb_seed_epoch();
 
+namespace vbemb {
+// vb_text_embed_bwd under the deterministic setting (embed_bwd.hip): 0 = the ordered kernels ran on the stream's
+// workspace slice; -1 = the setting is off, or there is no slice / it is too small (counted by
+// vb_deterministic_fallbacks) - the caller runs the atomic kernels; > 0 = launch error (hipError_t)
+int text_embed_bwd_det(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
+                       const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
+                       float* dpos, float* dtype, float* dtask);
+}  // namespace vbemb
+
 static inline bool vb_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -826,6 +826,10 @@ extern "C" int vb_text_embed_bwd(void* stream, int32_t batch, int32_t n_tok, int
     if (int e = check_cols(hidden)) return e;
     if (!vb_aligned16(dx)) return VB_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // deterministic setting: the ordered keyed reduction (embed_bwd.hip); without a workspace slice, the atomics below
+    const int ordered = vbemb::text_embed_bwd_det(st, batch, n_tok, hidden, vocab, n_types, n_tasks, ids, seg, task_ids,
+                                                  dx, dword, dpos, dtype, dtask);
+    if (ordered >= 0) return ordered;
     const long rows = (long)batch * (n_tok + (task_ids != nullptr ? 1 : 0));
     dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), block(256);
     VB_NV_DISPATCH(nv_for(hidden), hipLaunchKernelGGL((text_embed_scatter_kernel<NV>), grid, block, 0, st, batch,

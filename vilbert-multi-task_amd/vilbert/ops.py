@@ -664,11 +664,13 @@ def text_embed_ln_fwd(ids, seg, word, pos, typ, gamma, beta, eps, task_ids=None,
 
 def text_embed_bwd(dx, ids, seg, task_ids, word_shape, pos_shape, type_shape, task_shape, out=None):
     """Scatter-add dx (gradient of the pre-LayerNorm sum) into zero tables (fresh ones, or the accumulating targets
-    `out` = [dword, dpos, dtype, dtask] with None for the ones to allocate)."""
+    `out` = [dword, dpos, dtype, dtask] with None for the ones to allocate). Deterministic setting on: the ordered
+    keyed reduction of include/vilbert_hip.h on the device's workspace (registered here if no GEMM did yet)."""
     dx = _contig(dx)
     ids, seg = _contig(ids), _contig(seg)
     B, T = ids.shape
     dev = dx.device
+    N.ensure_deterministic(dev)
     out = out if out is not None else [None] * 4
     dword = out[0] if out[0] is not None else torch.zeros(word_shape, dtype=torch.float32, device=dev)
     dpos = out[1] if out[1] is not None else torch.zeros(pos_shape, dtype=torch.float32, device=dev)
