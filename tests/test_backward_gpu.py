@@ -146,6 +146,37 @@ def test_attention_backward_into_fused_buffers(ops):
     _close(dqkv, q64.grad)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_bi_attention_node_with_one_direction_in_the_loss(dtype):
+    """autograd_ops.BiAttnFn on the fp32 and the bf16 stream when only ctx2 reaches the loss: the other direction gets a zero
+    gradient in ctx1's shape, and dqkv1 / dqkv2 match float64 autograd through the oracle attention (bf16: the bound of
+    test_bf16_stream_gpu's attention check). The batches are equal: the attention backward kernels take no broadcast batch."""
+    from vilbert import autograd_ops as AO
+    B, heads, d, S1, S2 = 4, 2, 64, 24, 20
+    H = heads * d
+    qkv1 = (_rand(B, S1, 3 * H, seed=31) * 0.7).to(dtype)
+    qkv2 = (_rand(B, S2, 3 * H, seed=32) * 0.7).to(dtype)
+    g = torch.Generator().manual_seed(33)
+    m1, m2 = ((torch.rand(B, S, generator=g) < 0.2).float() * -10000.0 for S in (S1, S2))
+    m1[:, 0] = m2[:, 0] = 0.0
+    d2 = _rand(B, S1, H, seed=34).to(dtype)
+    x1, x2 = qkv1.to(DEV).requires_grad_(True), qkv2.to(DEV).requires_grad_(True)
+    c1, c2, _, _ = AO.BiAttnFn.apply(x1, x2, m1.to(DEV), m2.to(DEV), heads, 0.0, 0.0, False)
+    assert c1.shape == (B, S2, H) and c2.shape == (B, S1, H)
+    c2.backward(d2.to(DEV))
+    r1, r2 = qkv1.double().requires_grad_(True), qkv2.double().requires_grad_(True)
+    vo._attend(r1[..., :H], r2[..., H:2 * H], r2[..., 2 * H:], m2.double().view(B, 1, 1, S2), heads)[0].backward(d2.double())
+    for got, want in ((x1.grad, r1.grad), (x2.grad, r2.grad)):
+        if dtype == torch.float32:
+            _close(got, want)
+            continue
+        got = got.cpu().double()
+        assert torch.isfinite(got).all()
+        l2 = float((got - want).norm() / want.norm())
+        mx = float((got - want).abs().max() / want.abs().max())
+        assert l2 <= 1.5e-2 and mx <= 2.0 ** -6, "relative L2 %.3e, max error %.3e of the range" % (l2, mx)
+
+
 def _grad_parity(cfg, kind, batch, n_tok, n_reg, seed=5):
     from vilbert.vilbert import BertConfig, BertForMultiModalPreTraining, VILBertForVLTasks
     sd = synth.make_state_dict(cfg, kind, seed=seed)

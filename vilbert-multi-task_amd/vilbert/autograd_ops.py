@@ -14,6 +14,9 @@ from torch.autograd import Function
 from . import _native as N
 from . import arena as _arena
 from . import ops
+from . import ops16
+
+BF16 = torch.bfloat16
 
 _seed_counter = itertools.count(1)
 
@@ -23,6 +26,31 @@ def next_seed():
     with a per-process call counter. No device sync."""
     return ((torch.initial_seed() & 0xFFFFFFFF) * 0x9E3779B1 + next(_seed_counter) * 0x632BE59BD9B4E019) \
         & 0xFFFFFFFFFFFFFFFF
+
+
+# bf16 TRAINING path (round 5; ops16.py, csrc/gemm_bf16.hip): the nodes below serve both streams - on bfloat16 activations they
+# launch the ops16 kernels, otherwise the ops ones. Parameters, their gradients (arena slices, fp32), LayerNorm statistics and
+# the softmax statistics stay fp32. What the reference does with `model.half()` + apex FP16_Optimizer
+# (train_concap.py:443-461,504-505), without loss scaling (bf16 keeps fp32's exponent range).
+def _ops(t):
+    """Launcher module of t's stream. Callers look the launcher up on it at call time, never bind it at import."""
+    return ops16 if t.dtype == BF16 else ops
+
+
+# the two launchers whose bf16 form takes other arguments: ops16.linear_bwd_input has a (unused) biases slot,
+# ops16.attention_fwd has no probabilities tensor
+def _dgrad(dy, weights, in_features, residual=None, mul=None):
+    if dy.dtype == BF16:
+        return ops16.linear_bwd_input(dy, weights, None, in_features, residual, mul)
+    return ops.linear_bwd_input(dy, weights, in_features, residual, mul)
+
+
+def attention_fwd(q, k, v, mask_add, heads, want_probs, want_lse, drop_p, seed):
+    """ops.attention_fwd's contract on either stream: (ctx, probs or None, lse or None); bf16 has no probabilities."""
+    if q.dtype == BF16:
+        out, lse = ops16.attention_fwd(q, k, v, mask_add, heads, want_lse, drop_p, seed)
+        return out, None, lse
+    return ops.attention_fwd(q, k, v, mask_add, heads, want_probs, want_lse, drop_p, seed)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -136,8 +164,8 @@ class _Claims(object):
 
 def _wgrad(dy, x, weights, biases_present, need_w, need_b, launcher=None):
     """dW / db of the stacked segments into their arena slices (or fresh buffers); returns what autograd gets.
-    launcher: ops.linear_bwd_weight (fp32 tensors, default) or ops16.linear_bwd_weight (bf16 tensors) - same contract."""
-    launcher = launcher or ops.linear_bwd_weight
+    launcher: linear_bwd_weight of dy's stream (default) or another launcher with its contract."""
+    launcher = launcher or _ops(dy).linear_bwd_weight
     nseg, seg_n = len(weights), weights[0].shape[0]
     cw = _Claims(weights, need_w)
     cb = _Claims(biases_present, need_b)
@@ -162,17 +190,20 @@ def _wgrad(dy, x, weights, biases_present, need_w, need_b, launcher=None):
 
 
 class LinearFn(Function):
-    """y = dropout(act(x @ cat(W).T + cat(b)), p) (+ residual). Inputs: x, residual, act, nseg, drop_p, W..., b...
+    """y = dropout(act(x @ cat(W).T + cat(b)), p) (+ residual). Inputs: x, residual, act, nseg, drop_p, pad_cols, out_f32,
+    W..., b... pad_cols (fp32 x): see ops.linear_fwd. out_f32 (bf16 x): y is fp32 (the image-feature projection in front of
+    the fp32 embedding kernel). A bf16 x comes without act (functional.linear runs such a linear on the fp32 kernels).
     The dropout mask is regenerated in backward from the saved seed (vb_dropout on the incoming gradient)."""
 
     @staticmethod
-    def forward(ctx, x, residual, act, nseg, drop_p, *wb):
-        pad_cols = nseg < 0          # (flag folded into the sign of nseg: the output keeps a 16-byte row stride)
-        nseg = abs(nseg)
+    def forward(ctx, x, residual, act, nseg, drop_p, pad_cols, out_f32, *wb):
         weights, biases = list(wb[:nseg]), list(wb[nseg:])
         seed = next_seed() if drop_p > 0.0 else 0
-        y, pre = ops.linear_fwd(x, weights, biases, act, residual, want_preact=act is not None, drop_p=drop_p,
-                                seed=seed, pad_cols=pad_cols)
+        if x.dtype == BF16:
+            y, pre = ops16.linear_fwd(x, weights, biases, act, residual, drop_p=drop_p, seed=seed, out_f32=out_f32)
+        else:
+            y, pre = ops.linear_fwd(x, weights, biases, act, residual, want_preact=act is not None, drop_p=drop_p,
+                                    seed=seed, pad_cols=pad_cols)
         ctx.save_for_backward(x, pre, *weights, *[b for b in biases if b is not None])
         ctx.act, ctx.nseg = act, nseg
         ctx.drop = (drop_p, seed)
@@ -187,27 +218,31 @@ class LinearFn(Function):
         rest = list(ctx.saved_tensors[2 + nseg:])
         biases = [rest.pop(0) if h else None for h in ctx.has_bias]
         seg_n, K = weights[0].shape[0], weights[0].shape[1]
-        if not (ops._row_strided(dy) and ctx.drop[0] == 0.0 and ctx.act is None and not ctx.needs_input_grad[1]):
-            dy = dy.contiguous()     # (a row-strided gradient of padded logits feeds the GEMMs in place)
+        if dy.dtype != x.dtype:      # out_f32: the gradient of the fp32 output arrives in fp32
+            dy = ops16.cast_bf16(dy)
+        elif x.dtype == BF16 or not (ops._row_strided(dy) and ctx.drop[0] == 0.0 and ctx.act is None
+                                     and not ctx.needs_input_grad[1]):
+            dy = dy.contiguous()     # (a row-strided gradient of padded fp32 logits feeds the GEMMs in place)
         dres = dy if ctx.needs_input_grad[1] else None
         if ctx.drop[0] > 0.0:
             dy = _dropped(dy, ctx.drop)
         dpre = ops.act_bwd(dy, pre, ctx.act) if ctx.act is not None else dy
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = ops.linear_bwd_input(dpre, weights, K).view(x.shape)
-        need_w = [bool(ctx.needs_input_grad[5 + s]) for s in range(nseg)]
-        need_b = [ctx.has_bias[s] and ctx.needs_input_grad[5 + nseg + s] for s in range(nseg)]
+            dx = _dgrad(dpre, weights, K).view(x.shape)
+        need_w = [bool(ctx.needs_input_grad[7 + s]) for s in range(nseg)]
+        need_b = [ctx.has_bias[s] and ctx.needs_input_grad[7 + nseg + s] for s in range(nseg)]
         dws, dbs = [None] * nseg, [None] * nseg
         if any(need_w) or any(need_b):
             # (the fused launch computes every segment; segments nobody asked for land in scratch buffers)
             launcher = None
-            if nseg == 1 and dpre.is_cuda and ops16.ragged_wgrad_ok(seg_n, K, dpre.numel() // max(seg_n, 1)):
+            if (x.dtype != BF16 and nseg == 1 and dpre.is_cuda
+                    and ops16.ragged_wgrad_ok(seg_n, K, dpre.numel() // max(seg_n, 1))):
                 # bf16 mode: the wide ragged heads (30,522-wide MLM decoder) on the bf16 weight-gradient kernel
                 launcher = lambda dy_, x_, nseg_, seg_n_, want_b, dw_out=None, db_out=None: \
                     ops16.linear_bwd_weight_ragged(dy_, x_, want_b, dw_out, db_out)
             dws, dbs = _wgrad(dpre, x, weights, biases, need_w, need_b, launcher)
-        return (dx, dres, None, None, None) + tuple(dws) + tuple(dbs)
+        return (dx, dres, None, None, None, None, None) + tuple(dws) + tuple(dbs)
 
 
 class FFNFn(Function):
@@ -221,8 +256,8 @@ class FFNFn(Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, act, drop_p):
         seed = next_seed() if drop_p > 0.0 else 0
-        h, dact = ops.linear_fwd(x, [w1], [b1], act, None, want_act_grad=True)
-        y, _ = ops.linear_fwd(h, [w2], [b2], None, x, drop_p=drop_p, seed=seed)
+        h, dact = _ops(x).linear_fwd(x, [w1], [b1], act, None, want_act_grad=True)
+        y, _ = _ops(x).linear_fwd(h, [w2], [b2], None, x, drop_p=drop_p, seed=seed)
         ctx.save_for_backward(x, dact, h, w1, w2, *[b for b in (b1, b2) if b is not None])
         ctx.act, ctx.drop = act, (drop_p, seed)
         ctx.has_bias = (b1 is not None, b2 is not None)
@@ -237,13 +272,13 @@ class FFNFn(Function):
         dy = dy.contiguous()
         dyd = _dropped(dy, ctx.drop) if ctx.drop[0] > 0.0 else dy
         inter, hidden = w1.shape[0], w1.shape[1]
-        dpre = ops.linear_bwd_input(dyd, [w2], inter, mul=dact)
+        dpre = _dgrad(dyd, [w2], inter, mul=dact)
         dw2 = db2 = dw1 = db1 = dx = None
         nb2 = bool(ctx.has_bias[1] and ctx.needs_input_grad[4])
         if ctx.needs_input_grad[3] or nb2:
             (dw2,), (db2,) = _wgrad(dyd, h, [w2], [b2], [bool(ctx.needs_input_grad[3])], [nb2])
         if ctx.needs_input_grad[0]:
-            dx = ops.linear_bwd_input(dpre, [w1], hidden, residual=dy).view(x.shape)
+            dx = _dgrad(dpre, [w1], hidden, residual=dy).view(x.shape)
         nb1 = bool(ctx.has_bias[0] and ctx.needs_input_grad[2])
         if ctx.needs_input_grad[1] or nb1:
             (dw1,), (db1,) = _wgrad(dpre, x, [w1], [b1], [bool(ctx.needs_input_grad[1])], [nb1])
@@ -254,7 +289,7 @@ def _ln_bwd(dy, x, mean, rstd, gamma, beta, need_g, need_b, drop=None):
     """LayerNorm backward with dgamma / dbeta written straight into their arena slices when those are fresh.
     drop = (p, seed) of the dense layer in front: dx comes back tagged with its dropout-masked twin (see _DROP_HINT)."""
     c = _Claims([gamma, beta], [need_g, need_b])
-    res = ops.layernorm_bwd(dy, x, mean, rstd, gamma, c.fresh_or_none(0), c.fresh_or_none(1), drop=drop)
+    res = _ops(x).layernorm_bwd(dy, x, mean, rstd, gamma, c.fresh_or_none(0), c.fresh_or_none(1), drop=drop)
     dx, dgamma, dbeta = res[:3]
     if len(res) == 4:
         dx._vb_dropped = (drop[0], drop[1], res[3], dx.data_ptr(), dx._version)
@@ -283,15 +318,15 @@ def _dropped(dy, drop):
     if (tag is not None and tag[0] == drop[0] and tag[1] == drop[1] and tag[2].shape == dy.shape
             and tag[3] == dy.data_ptr() and tag[4] == dy._version):
         return tag[2]
-    return ops.dropout(dy, drop[0], drop[1])
+    return _ops(dy).dropout(dy, drop[0], drop[1])
 
 
 class LayerNormFn(Function):
-    """TF-style LayerNorm of one tensor."""
+    """TF-style LayerNorm of one tensor (statistics fp32 on both streams)."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        y, mean, rstd = ops.layernorm_fwd(x, gamma, beta, eps, None, want_stats=True)
+        y, mean, rstd = _ops(x).layernorm_fwd(x, gamma, beta, eps, want_stats=True)
         ctx.save_for_backward(x, mean, rstd, gamma, beta)
         ctx.drop_hint = getattr(x, "_vb_drop", None)      # x = dropout(dense(h)) + residual of the node in front
         return y
@@ -344,11 +379,11 @@ class SelfAttnFn(Function):
         H = qkv.shape[-1] // 3
         _check_keys_for_backward(qkv.shape[1], want_probs)
         seed = next_seed() if drop_p > 0.0 else 0
-        out, probs, lse = ops.attention_fwd(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads,
-                                            want_probs, True, drop_p, seed)
+        out, probs, lse = attention_fwd(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads, want_probs,
+                                        True, drop_p, seed)
         ctx.save_for_backward(qkv, mask_add, lse)
         ctx.meta = (heads, drop_p, seed)
-        if probs is None:
+        if probs is None:                     # (none on the bf16 stream)
             probs = qkv.new_empty(0)
         ctx.mark_non_differentiable(probs)
         ctx.set_materialize_grads(False)      # no zeros() for the gradient slot of the non-differentiable probs
@@ -362,8 +397,8 @@ class SelfAttnFn(Function):
         heads, drop_p, seed = ctx.meta
         H = qkv.shape[-1] // 3
         dqkv = torch.empty_like(qkv)
-        ops.attention_bwd(d_out, qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads, lse,
-                          dqkv[..., :H], dqkv[..., H:2 * H], dqkv[..., 2 * H:], drop_p, seed)
+        _ops(qkv).attention_bwd(d_out, qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads, lse,
+                                dqkv[..., :H], dqkv[..., H:2 * H], dqkv[..., 2 * H:], drop_p, seed)
         return dqkv, None, None, None, None
 
 
@@ -380,10 +415,11 @@ class BiAttnFn(Function):
         s2 = next_seed() if p2 > 0.0 else 0
         q1, k1, v1 = qkv1[..., :H], qkv1[..., H:2 * H], qkv1[..., 2 * H:]
         q2, k2, v2 = qkv2[..., :H], qkv2[..., H:2 * H], qkv2[..., 2 * H:]
-        ctx1, probs1, lse1 = ops.attention_fwd(q2, k1, v1, mask1, heads, want_probs, True, p1, s1)
-        ctx2, probs2, lse2 = ops.attention_fwd(q1, k2, v2, mask2, heads, want_probs, True, p2, s2)
+        ctx1, probs1, lse1 = attention_fwd(q2, k1, v1, mask1, heads, want_probs, True, p1, s1)
+        ctx2, probs2, lse2 = attention_fwd(q1, k2, v2, mask2, heads, want_probs, True, p2, s2)
         ctx.save_for_backward(qkv1, qkv2, mask1, mask2, lse1, lse2)
         ctx.meta = (heads, p1, p2, s1, s2)
+        ctx.out_shapes = (ctx1.shape, ctx2.shape)      # (a batch of 1 broadcasts against the other stream's)
         if probs1 is None:
             probs1, probs2 = qkv1.new_empty(0), qkv1.new_empty(0)
         ctx.mark_non_differentiable(probs1, probs2)
@@ -397,9 +433,9 @@ class BiAttnFn(Function):
         if d1 is None and d2 is None:
             return (None,) * 8
         if d1 is None:                         # only one direction reached the loss: the other one's gradient is zero
-            d1 = torch.zeros((qkv2.shape[0], qkv2.shape[1], qkv1.shape[-1] // 3), dtype=qkv1.dtype, device=qkv1.device)
+            d1 = qkv1.new_zeros(ctx.out_shapes[0])
         if d2 is None:
-            d2 = torch.zeros((qkv1.shape[0], qkv1.shape[1], qkv1.shape[-1] // 3), dtype=qkv1.dtype, device=qkv1.device)
+            d2 = qkv1.new_zeros(ctx.out_shapes[1])
         H = qkv1.shape[-1] // 3
         sl = lambda t: (t[..., :H], t[..., H:2 * H], t[..., 2 * H:])
         q1, k1, v1 = sl(qkv1)
@@ -407,8 +443,8 @@ class BiAttnFn(Function):
         dqkv1, dqkv2 = torch.empty_like(qkv1), torch.empty_like(qkv2)
         dq1, dk1, dv1 = sl(dqkv1)
         dq2, dk2, dv2 = sl(dqkv2)
-        ops.attention_bwd(d1, q2, k1, v1, mask1, heads, lse1, dq2, dk1, dv1, p1, s1)
-        ops.attention_bwd(d2, q1, k2, v2, mask2, heads, lse2, dq1, dk2, dv2, p2, s2)
+        _ops(qkv1).attention_bwd(d1, q2, k1, v1, mask1, heads, lse1, dq2, dk1, dv1, p1, s1)
+        _ops(qkv1).attention_bwd(d2, q1, k2, v2, mask2, heads, lse2, dq1, dk2, dv2, p2, s2)
         return dqkv1, dqkv2, None, None, None, None, None, None
 
 
@@ -483,15 +519,6 @@ class KLDivFn(torch.autograd.Function):
         return ops.kl_bwd(grad_loss, scores, target, lse, tsum, ctx.divisor), None, None
 
 
-# ---------------------------------------------------------------------------------------------------------------
-# bf16 TRAINING path (round 5; ops16.py, csrc/gemm_bf16.hip): the same autograd nodes on bfloat16 activations. Parameters,
-# their gradients (arena slices, fp32), LayerNorm statistics and the softmax statistics stay fp32. What the reference does
-# with `model.half()` + apex FP16_Optimizer (train_concap.py:443-461,504-505), without loss scaling (bf16 keeps fp32's
-# exponent range).
-# ---------------------------------------------------------------------------------------------------------------
-from . import ops16  # noqa: E402
-
-
 class CastFn(Function):
     """fp32 <-> bfloat16 at the edges of the bf16 stream (embeddings in, sequence outputs out); backward = the other cast."""
 
@@ -503,175 +530,3 @@ class CastFn(Function):
     @staticmethod
     def backward(ctx, dy):
         return (ops16.cast_f32(dy) if ctx.to_bf16 else ops16.cast_bf16(dy)), None
-
-
-def _dropped16(dy, drop):
-    tag = getattr(dy, "_vb_dropped", None)
-    if (tag is not None and tag[0] == drop[0] and tag[1] == drop[1] and tag[2].shape == dy.shape
-            and tag[3] == dy.data_ptr() and tag[4] == dy._version):
-        return tag[2]
-    return ops16.dropout(dy, drop[0], drop[1])
-
-
-class Linear16Fn(Function):
-    """y = dropout(x @ cat(W).T + cat(b), p) (+ residual) on bf16 tensors (y fp32 when out_f32: the image-feature projection
-    in front of the fp32 embedding kernel). Inputs: x, residual, nseg, drop_p, out_f32, W..., b... (a linear with an
-    activation of its own is not an autograd node of this path: the FFN is FFN16Fn, functional.linear sends the rest
-    through the fp32 node)."""
-
-    @staticmethod
-    def forward(ctx, x, residual, nseg, drop_p, out_f32, *wb):
-        weights, biases = list(wb[:nseg]), list(wb[nseg:])
-        seed = next_seed() if drop_p > 0.0 else 0
-        y, _ = ops16.linear_fwd(x, weights, biases, None, residual, drop_p=drop_p, seed=seed, out_f32=out_f32)
-        ctx.save_for_backward(x, *weights, *[b for b in biases if b is not None])
-        ctx.nseg = nseg
-        ctx.drop = (drop_p, seed)
-        ctx.has_bias = [b is not None for b in biases]
-        return _tag_drop(y, drop_p, seed) if residual is not None else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x = ctx.saved_tensors[0]
-        nseg = ctx.nseg
-        weights = list(ctx.saved_tensors[1:1 + nseg])
-        rest = list(ctx.saved_tensors[1 + nseg:])
-        biases = [rest.pop(0) if h else None for h in ctx.has_bias]
-        K = weights[0].shape[1]
-        dy = dy.contiguous()
-        if dy.dtype != ops16.BF16:          # fp32 output: the gradient arrives in fp32
-            dy = ops16.cast_bf16(dy)
-        dres = dy if ctx.needs_input_grad[1] else None
-        if ctx.drop[0] > 0.0:
-            dy = _dropped16(dy, ctx.drop)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops16.linear_bwd_input(dy, weights, biases, K).view(x.shape)
-        need_w = [bool(ctx.needs_input_grad[5 + s]) for s in range(nseg)]
-        need_b = [ctx.has_bias[s] and ctx.needs_input_grad[5 + nseg + s] for s in range(nseg)]
-        dws, dbs = [None] * nseg, [None] * nseg
-        if any(need_w) or any(need_b):
-            dws, dbs = _wgrad(dy, x, weights, biases, need_w, need_b, launcher=ops16.linear_bwd_weight)
-        return (dx, dres, None, None, None) + tuple(dws) + tuple(dbs)
-
-
-class FFN16Fn(Function):
-    """y = dropout(gelu(x @ W1.T + b1) @ W2.T + b2, p) + x on bf16 tensors - FFNFn's structure: the up-projection's epilogue
-    stores gelu'(pre) next to the activation, the dgrad through W2 multiplies by it, the dgrad through W1 adds the skip
-    gradient; no elementwise pass over [M, intermediate] in either direction."""
-
-    @staticmethod
-    def forward(ctx, x, w1, b1, w2, b2, drop_p):
-        seed = next_seed() if drop_p > 0.0 else 0
-        h, dact = ops16.linear_fwd(x, [w1], [b1], "gelu", want_act_grad=True)
-        y, _ = ops16.linear_fwd(h, [w2], [b2], None, x, drop_p=drop_p, seed=seed)
-        ctx.save_for_backward(x, dact, h, w1, w2, *[b for b in (b1, b2) if b is not None])
-        ctx.drop = (drop_p, seed)
-        ctx.has_bias = (b1 is not None, b2 is not None)
-        return _tag_drop(y, drop_p, seed)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, dact, h, w1, w2 = ctx.saved_tensors[:5]
-        rest = list(ctx.saved_tensors[5:])
-        b1 = rest.pop(0) if ctx.has_bias[0] else None
-        b2 = rest.pop(0) if ctx.has_bias[1] else None
-        dy = dy.contiguous()
-        dyd = _dropped16(dy, ctx.drop) if ctx.drop[0] > 0.0 else dy
-        inter, hidden = w1.shape[0], w1.shape[1]
-        dpre = ops16.linear_bwd_input(dyd, [w2], [b2], inter, mul=dact)
-        dw2 = db2 = dw1 = db1 = dx = None
-        nb2 = bool(ctx.has_bias[1] and ctx.needs_input_grad[4])
-        if ctx.needs_input_grad[3] or nb2:
-            (dw2,), (db2,) = _wgrad(dyd, h, [w2], [b2], [bool(ctx.needs_input_grad[3])], [nb2], launcher=ops16.linear_bwd_weight)
-        if ctx.needs_input_grad[0]:
-            dx = ops16.linear_bwd_input(dpre, [w1], [b1], hidden, residual=dy).view(x.shape)
-        nb1 = bool(ctx.has_bias[0] and ctx.needs_input_grad[2])
-        if ctx.needs_input_grad[1] or nb1:
-            (dw1,), (db1,) = _wgrad(dpre, x, [w1], [b1], [bool(ctx.needs_input_grad[1])], [nb1], launcher=ops16.linear_bwd_weight)
-        return dx, dw1, db1, dw2, db2, None
-
-
-class LayerNorm16Fn(Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, eps):
-        y, mean, rstd = ops16.layernorm_fwd(x, gamma, beta, eps, want_stats=True)
-        ctx.save_for_backward(x, mean, rstd, gamma, beta)
-        ctx.drop_hint = getattr(x, "_vb_drop", None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mean, rstd, gamma, beta = ctx.saved_tensors
-        need_g, need_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        c = _Claims([gamma, beta], [need_g, need_b])
-        res = ops16.layernorm_bwd(dy, x, mean, rstd, gamma, c.fresh_or_none(0), c.fresh_or_none(1), drop=ctx.drop_hint)
-        dx, dgamma, dbeta = res[:3]
-        out = dx.view(x.shape)
-        if len(res) == 4:
-            out._vb_dropped = (ctx.drop_hint[0], ctx.drop_hint[1], res[3].view(x.shape), out.data_ptr(), out._version)
-        return (out, (c.finish_overwrite(0, dgamma) if need_g else None), (c.finish_overwrite(1, dbeta) if need_b else None),
-                None)
-
-
-class SelfAttn16Fn(Function):
-    """Attention over one fused bf16 [q | k | v] projection; context and dqkv bf16, softmax statistics fp32."""
-
-    @staticmethod
-    def forward(ctx, qkv, mask_add, heads, drop_p):
-        H = qkv.shape[-1] // 3
-        seed = next_seed() if drop_p > 0.0 else 0
-        out, lse = ops16.attention_fwd(qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads, True, drop_p, seed)
-        ctx.save_for_backward(qkv, mask_add, lse)
-        ctx.meta = (heads, drop_p, seed)
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        qkv, mask_add, lse = ctx.saved_tensors
-        heads, drop_p, seed = ctx.meta
-        H = qkv.shape[-1] // 3
-        dqkv = torch.empty_like(qkv)
-        ops16.attention_bwd(d_out, qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:], mask_add, heads, lse,
-                            dqkv[..., :H], dqkv[..., H:2 * H], dqkv[..., 2 * H:], drop_p, seed)
-        return dqkv, None, None, None
-
-
-class BiAttn16Fn(Function):
-    """Both directions of the co-attention on the two fused bf16 projections (BiAttnFn's structure)."""
-
-    @staticmethod
-    def forward(ctx, qkv1, qkv2, mask1, mask2, heads, p1, p2):
-        H = qkv1.shape[-1] // 3
-        s1 = next_seed() if p1 > 0.0 else 0
-        s2 = next_seed() if p2 > 0.0 else 0
-        sl = lambda t: (t[..., :H], t[..., H:2 * H], t[..., 2 * H:])
-        q1, k1, v1 = sl(qkv1)
-        q2, k2, v2 = sl(qkv2)
-        ctx1, lse1 = ops16.attention_fwd(q2, k1, v1, mask1, heads, True, p1, s1)
-        ctx2, lse2 = ops16.attention_fwd(q1, k2, v2, mask2, heads, True, p2, s2)
-        ctx.save_for_backward(qkv1, qkv2, mask1, mask2, lse1, lse2)
-        ctx.meta = (heads, p1, p2, s1, s2)
-        ctx.set_materialize_grads(False)
-        return ctx1, ctx2
-
-    @staticmethod
-    def backward(ctx, d1, d2):
-        qkv1, qkv2, mask1, mask2, lse1, lse2 = ctx.saved_tensors
-        heads, p1, p2, s1, s2 = ctx.meta
-        if d1 is None and d2 is None:
-            return (None,) * 7
-        H = qkv1.shape[-1] // 3
-        if d1 is None:
-            d1 = torch.zeros((max(qkv1.shape[0], qkv2.shape[0]), qkv2.shape[1], H), dtype=qkv1.dtype, device=qkv1.device)
-        if d2 is None:
-            d2 = torch.zeros((max(qkv1.shape[0], qkv2.shape[0]), qkv1.shape[1], H), dtype=qkv1.dtype, device=qkv1.device)
-        sl = lambda t: (t[..., :H], t[..., H:2 * H], t[..., 2 * H:])
-        q1, k1, v1 = sl(qkv1)
-        q2, k2, v2 = sl(qkv2)
-        dqkv1, dqkv2 = torch.empty_like(qkv1), torch.empty_like(qkv2)
-        dq1, dk1, dv1 = sl(dqkv1)
-        dq2, dk2, dv2 = sl(dqkv2)
-        ops16.attention_bwd(d1, q2, k1, v1, mask1, heads, lse1, dq2, dk1, dv1, p1, s1)
-        ops16.attention_bwd(d2, q1, k2, v2, mask2, heads, lse2, dq1, dk2, dv2, p2, s2)
-        return dqkv1, dqkv2, None, None, None, None, None

@@ -726,7 +726,8 @@ def additive_mask(mask):
     return out
 
 
-def _attn_args(q, k, v, mask_add, heads, drop_p, seed):
+def _attn_args(q, k, v, mask_add, heads, drop_p, seed, dev=N.dev_f32):
+    """AttentionArgs of one launch; dev: the pointer checker of q / k / v (N.dev_f32, or ops16.dev_bf16 on the bf16 path)."""
     Bq, Sq, H = q.shape
     Bk, Sk, _ = k.shape
     B = max(Bq, Bk)
@@ -737,9 +738,9 @@ def _attn_args(q, k, v, mask_add, heads, drop_p, seed):
     a = N.AttentionArgs()
     a.batch, a.heads, a.head_dim, a.n_q, a.n_k = B, heads, d, Sq, Sk
     a.q_batch, a.kv_batch = Bq, Bk
-    a.Q, a.ldq = N.dev_f32(q, "attention q"), q.stride(1)
-    a.K, a.ldk = N.dev_f32(k, "attention k"), k.stride(1)
-    a.V, a.ldv = N.dev_f32(v, "attention v"), v.stride(1)
+    a.Q, a.ldq = dev(q, "attention q"), q.stride(1)
+    a.K, a.ldk = dev(k, "attention k"), k.stride(1)
+    a.V, a.ldv = dev(v, "attention v"), v.stride(1)
     keep = []
     if mask_add is not None:
         mask_add = _contig(mask_add)

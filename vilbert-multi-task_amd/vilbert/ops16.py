@@ -10,7 +10,6 @@ captured graphs keep their addresses).
 """
 import ctypes
 import os
-import math
 import weakref
 
 import torch
@@ -396,38 +395,12 @@ def dropout(x, p, seed):
     return cast_bf16(ops.dropout(cast_f32(x), p, seed))
 
 
-def _attn_args16(q, k, v, mask_add, heads, drop_p, seed):
-    Bq, Sq, H = q.shape
-    Bk, Sk, _ = k.shape
-    B = max(Bq, Bk)
-    d = H // heads
-    for t, nm in ((q, "q"), (k, "k"), (v, "v")):
-        if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise RuntimeError("attention: %s must be a row-strided view" % nm)
-    a = N.AttentionArgs()
-    a.batch, a.heads, a.head_dim, a.n_q, a.n_k = B, heads, d, Sq, Sk
-    a.q_batch, a.kv_batch = Bq, Bk
-    a.Q, a.ldq = dev_bf16(q, "attention q"), q.stride(1)
-    a.K, a.ldk = dev_bf16(k, "attention k"), k.stride(1)
-    a.V, a.ldv = dev_bf16(v, "attention v"), v.stride(1)
-    keep = []
-    if mask_add is not None:
-        mask_add = ops._contig(mask_add)
-        if mask_add.numel() != Bk * Sk:
-            raise RuntimeError("attention: mask must hold %d x %d values" % (Bk, Sk))
-        a.mask_add = N.dev_f32(mask_add, "attention mask")
-        keep.append(mask_add)
-    a.scale = 1.0 / math.sqrt(d)
-    a.dropout_p, a.seed = float(drop_p), int(seed)
-    return a, keep, (B, Sq, Sk, H)
-
-
 def attention_fwd(q, k, v, mask_add, heads, want_lse=False, drop_p=0.0, seed=0):
     """bf16 q [Bq, Sq, H*], k / v [Bk, Sk, H*] row-strided views (column slices of the fused projection); fp32 additive mask.
     Returns (ctx bf16 [B, Sq, H], lse fp32 [B, heads, Sq] or None). At most ops.MAX_KEYS keys."""
     if k.shape[1] > ops.MAX_KEYS:
         raise RuntimeError("attention (bf16): %d keys - one launch serves at most %d" % (k.shape[1], ops.MAX_KEYS))
-    a, keep, (B, Sq, Sk, H) = _attn_args16(q, k, v, mask_add, heads, drop_p, seed)
+    a, keep, (B, Sq, Sk, H) = ops._attn_args(q, k, v, mask_add, heads, drop_p, seed, dev_bf16)
     out = torch.empty(B, Sq, H, dtype=BF16, device=q.device)
     lse = torch.empty(B, heads, Sq, dtype=torch.float32, device=q.device) if want_lse else None
     a.O, a.ldo = out.data_ptr(), H
@@ -438,7 +411,7 @@ def attention_fwd(q, k, v, mask_add, heads, want_lse=False, drop_p=0.0, seed=0):
 
 def attention_bwd(d_out, q, k, v, mask_add, heads, lse, dq, dk, dv, drop_p=0.0, seed=0):
     """Writes dq / dk / dv (bf16 row-strided views, e.g. column slices of one fused gradient buffer) in place."""
-    a, keep, (B, Sq, Sk, H) = _attn_args16(q, k, v, mask_add, heads, drop_p, seed)
+    a, keep, (B, Sq, Sk, H) = ops._attn_args(q, k, v, mask_add, heads, drop_p, seed, dev_bf16)
     d_out = ops._contig(d_out)
     a.lse = N.dev_f32(lse, "attention lse")
     g = N.AttentionGrads()
