@@ -105,7 +105,7 @@ class _Targets(object):
         self.params = params
         if any(c[1] == "accum" for c in self.claims):
             A.join_wgrad_streams()          # an earlier writer of such a slice may still run on a side stream
-        need = sum((p.numel() + 3) // 4 * 4 for p, c in zip(params, self.claims) if c[0] is None)
+        need = sum(ops.align4(p.numel()) for p, c in zip(params, self.claims) if c[0] is None)
         self.scratch = torch.zeros(need, dtype=torch.float32, device=device) if need else None
         self.views, off = [], 0
         for p, c in zip(params, self.claims):
@@ -114,7 +114,7 @@ class _Targets(object):
             else:
                 n = p.numel()
                 self.views.append(self.scratch[off:off + n].view(p.shape))
-                off += (n + 3) // 4 * 4
+                off += ops.align4(n)
         self.all_fresh = all(c[1] == "fresh" for c in self.claims)
         self._tmp = None
 

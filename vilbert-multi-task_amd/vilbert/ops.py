@@ -5,12 +5,12 @@ and enqueues exactly the kernels of include/vilbert_hip.h on the current stream.
 """
 import ctypes
 import os as _os
-import weakref
 import math
 
 import torch
 
 from . import _native as N
+from .weight_cache import DerivedWeights
 
 
 # Optional per-launch timing of the GEMM kernel (bench.py's roofline leg): when enabled every GEMM
@@ -85,8 +85,6 @@ def _row_strided(t):
 # FP8 forward path (BASELINE config 5; numerics: oracle/fp8_oracle.py, kernels: csrc/fp8.hip)
 # ---------------------------------------------------------------------------------------------------------------
 FP8_K_MULTIPLE = 128     # the fp8 kernel's K step
-_FP8_WEIGHTS = {}        # (data_ptr of every segment) -> (versions, weights epoch, codes [N, K] u8, scales [N], bias [N])
-_WEIGHTS_EPOCH = N.WEIGHTS_EPOCH   # bumped by the native optimizer (parameters rewritten behind torch's version counters)
 
 
 def quantize_rows_fp8(x2, out=None, scale_out=None):
@@ -101,57 +99,49 @@ def quantize_rows_fp8(x2, out=None, scale_out=None):
     return q, sc
 
 
-def fp8_cache_clear():
-    _FP8_WEIGHTS.clear()
+class _Fp8Weight(object):
+    """Quantised copy of a (stacked) weight: q codes [N, K] uint8, s scales [N], bias [N] (the concatenated biases) or None."""
+    __slots__ = ("q", "s", "bias")
 
 
-def _fp8_sweep():
-    """Drop the entries whose weights nobody else holds any more (their model was deleted)."""
-    dead = [k for k, e in _FP8_WEIGHTS.items() if all(r() is None for r in e[6])]
-    for k in dead:
-        del _FP8_WEIGHTS[k]
-
-
-def _fp8_weights(weights, biases):
-    """Quantised copy of the (stacked) weight, cached until a segment is rewritten. The entry keeps an alias of every
-    segment alive, so a key (the segments' addresses) can never be recycled by a different tensor while it is cached;
-    entries whose weight tensors (the nn.Parameter objects the callers pass) are gone are dropped at the next miss."""
-    key = tuple(w.data_ptr() for w in weights)
-    vers = tuple(w._version for w in weights) + tuple(-1 if b is None else b._version for b in (biases or []))
+def _codes_fit(p, weights, n_pad):
     seg_n, K = weights[0].shape
-    n = seg_n * len(weights)
-    hit = _FP8_WEIGHTS.get(key)
-    if hit is not None and hit[2].shape != (n, K):
-        hit = None                                  # same address, different view of a buffer
-    if hit is not None and hit[0] == vers and hit[1] == _WEIGHTS_EPOCH[0]:
-        return hit[2], hit[3], hit[4]
-    dev = weights[0].device
-    if hit is not None:
-        q, sc, bias = hit[2], hit[3], hit[4]        # refresh in place: same addresses (HIP graphs keep them)
-    else:
-        _fp8_sweep()
-        q = torch.empty((n, K), dtype=torch.uint8, device=dev)
-        sc = torch.empty((n,), dtype=torch.float32, device=dev)
-        bias = None
-    with torch.no_grad():
-        for s, w in enumerate(weights):
-            quantize_rows_fp8(w.detach(), q[s * seg_n:(s + 1) * seg_n], sc[s * seg_n:(s + 1) * seg_n])
-        if biases is not None and all(b is not None for b in biases):
-            if len(biases) == 1:
-                bias = biases[0].detach()
-            elif bias is None:
-                bias = torch.cat([b.detach() for b in biases])
-            else:
-                # refresh in place: the concatenation kernel writes the cached buffer itself (no temporary + device-to-device
-                # copy, which inside a captured step is a memcpy node between two kernel nodes)
-                torch.cat([b.detach() for b in biases], out=bias)
-        elif biases is not None and any(b is not None for b in biases):
-            raise RuntimeError("linear (fp8): either every weight segment has a bias or none")
+    return p.q.shape == (n_pad or seg_n * len(weights), K)
+
+
+def _fp8_build(weights, biases, _hint):
+    seg_n, K = weights[0].shape
+    n, dev = seg_n * len(weights), weights[0].device
+    p = _Fp8Weight()
+    p.q = torch.empty((n, K), dtype=torch.uint8, device=dev)
+    p.s = torch.empty((n,), dtype=torch.float32, device=dev)
+    p.bias = None
+    _fp8_refresh(p, weights, biases)
+    return p
+
+
+def _fp8_refresh(p, weights, biases):
+    seg_n = weights[0].shape[0]
+    for s, w in enumerate(weights):
+        quantize_rows_fp8(w.detach(), p.q[s * seg_n:(s + 1) * seg_n], p.s[s * seg_n:(s + 1) * seg_n])
+    if biases is not None and all(b is not None for b in biases):
+        if len(biases) == 1:
+            p.bias = biases[0].detach()
+        elif p.bias is None:
+            p.bias = torch.cat([b.detach() for b in biases])
         else:
-            bias = None
-    _FP8_WEIGHTS[key] = (vers, _WEIGHTS_EPOCH[0], q, sc, bias, [w.detach() for w in weights],
-                         [weakref.ref(w) for w in weights])
-    return q, sc, bias
+            # refresh in place: the concatenation kernel writes the cached buffer itself (no temporary + device-to-device
+            # copy, which inside a captured step is a memcpy node between two kernel nodes)
+            torch.cat([b.detach() for b in biases], out=p.bias)
+    elif biases is not None and any(b is not None for b in biases):
+        raise RuntimeError("linear (fp8): either every weight segment has a bias or none")
+    else:
+        p.bias = None
+
+
+# the quantised weights, cached until a segment (or a bias) is rewritten: weight_cache.py
+_FP8_WEIGHTS = DerivedWeights(_fp8_build, _fp8_refresh, fits=_codes_fit, bias_versions=True)
+fp8_cache_clear = _FP8_WEIGHTS.clear
 
 
 def _fp8_eligible(x2, K, n_out, biases):
@@ -162,7 +152,7 @@ def _fp8_eligible(x2, K, n_out, biases):
 
 
 def _linear_fwd_fp8(x, x2, M, K, weights, biases, n_out, y, ldc, act, residual, pre, want_act_grad, drop_p, seed):
-    wq, ws, bias = _fp8_weights(weights, biases)
+    wc = _FP8_WEIGHTS.get(weights, biases)
     pre_q = getattr(x, "_vb_fp8", None)     # codes emitted by the producing LayerNorm (layernorm_fwd)
     if pre_q is not None and pre_q[2] == x._version and pre_q[0].shape == (M, K) and x.is_contiguous():
         xq, xs = pre_q[0], pre_q[1]
@@ -170,8 +160,8 @@ def _linear_fwd_fp8(x, x2, M, K, weights, biases, n_out, y, ldc, act, residual, 
         xq, xs = quantize_rows_fp8(x2)
     a = N.LinearFp8Args()
     a.A, a.lda, a.a_scale = xq.data_ptr(), K, xs.data_ptr()
-    a.W, a.ldw, a.w_scale = wq.data_ptr(), K, ws.data_ptr()
-    a.bias = N.dev_f32(bias, "linear bias") if bias is not None else None
+    a.W, a.ldw, a.w_scale = wc.q.data_ptr(), K, wc.s.data_ptr()
+    a.bias = N.dev_f32(wc.bias, "linear bias") if wc.bias is not None else None
     a.C, a.ldc = y.data_ptr(), ldc
     if residual is not None:
         a.residual, a.ldr = N.dev_f32(residual, "linear residual"), n_out
@@ -192,7 +182,6 @@ def _linear_fwd_fp8(x, x2, M, K, weights, biases, n_out, y, ldc, act, residual, 
 # ---------------------------------------------------------------------------------------------------------------
 MX_BLOCK = 32            # elements per scale
 MX_K_MULTIPLE = 128      # K of a linear (= the 4 scale bytes of one uint32 word), also the GEMM's column tile
-_MX_WEIGHTS = {}
 
 
 class MxRows(object):
@@ -235,54 +224,49 @@ def quantize_rows_mx(x2, lead=None, out=None):
     return m
 
 
-def mx_cache_clear():
-    _MX_WEIGHTS.clear()
+class _MxWeight(MxRows):
+    """MX copy of a (stacked) weight, plus `bias` = the concatenated biases [rows] or None."""
+    __slots__ = ("bias",)
 
 
-def _mx_weights(weights, biases, n_pad=None):
-    """MX copy of the (stacked) weight, cached like `_fp8_weights` (same invalidation rules). n_pad > rows: the copy has
-    n_pad rows, the extra ones all-zero codes with scale byte 0 (a head whose width is not a multiple of the GEMM's 128-column
-    tile: its extra output columns are computed as 0 + 0 and never shown)."""
-    key = tuple(w.data_ptr() for w in weights)
-    vers = tuple(w._version for w in weights) + tuple(-1 if b is None else b._version for b in (biases or []))
+def _mx_build(weights, biases, n_pad):
+    """n_pad > rows: the copy has n_pad rows, the extra ones all-zero codes with scale byte 0 (a head whose width is not a
+    multiple of the GEMM's 128-column tile: its extra output columns are computed as 0 + 0 and never shown)."""
     seg_n, K = weights[0].shape
     n_real = seg_n * len(weights)
-    n = n_real if n_pad is None else n_pad
-    hit = _MX_WEIGHTS.get(key)
-    if hit is not None and hit[2].q.shape != (n, K):
-        hit = None
-    if hit is not None and hit[0] == vers and hit[1] == _WEIGHTS_EPOCH[0]:
-        return hit[2], hit[3]
-    dev = weights[0].device
-    if hit is not None:
-        m, bias = hit[2], hit[3]                    # refresh in place (captured graphs keep the addresses)
-    else:
-        dead = [k for k, e in _MX_WEIGHTS.items() if all(r() is None for r in e[5])]
-        for k in dead:
-            del _MX_WEIGHTS[k]
-        m, bias = MxRows(n, K, dev, (n,)), None
-        if n != n_real:
-            m.q.zero_()
-            m.s.zero_()
-    with torch.no_grad():
-        cat = weights[0].detach() if len(weights) == 1 else torch.cat([w.detach() for w in weights])
-        quantize_rows_mx(cat, out=m)                # writes rows [0, n_real) of the codes and of every scale plane
-        if biases is not None and all(b is not None for b in biases):
-            bcat = biases[0].detach() if len(biases) == 1 else torch.cat([b.detach() for b in biases])
-            if n != n_real:
-                if bias is None:
-                    bias = torch.zeros(n, dtype=torch.float32, device=dev)
-                bias[:n_real].copy_(bcat)
-            elif bias is None or len(biases) == 1:
-                bias = bcat
-            else:
-                bias.copy_(bcat)
-        elif biases is not None and any(b is not None for b in biases):
-            raise RuntimeError("linear (mx): either every weight segment has a bias or none")
+    n = n_pad or n_real
+    m = _MxWeight(n, K, weights[0].device, (n,))
+    m.bias = None
+    if n != n_real:
+        m.q.zero_()
+        m.s.zero_()
+    _mx_refresh(m, weights, biases)
+    return m
+
+
+def _mx_refresh(m, weights, biases):
+    n_real = weights[0].shape[0] * len(weights)
+    cat = weights[0].detach() if len(weights) == 1 else torch.cat([w.detach() for w in weights])
+    quantize_rows_mx(cat, out=m)                    # writes rows [0, n_real) of the codes and of every scale plane
+    if biases is not None and all(b is not None for b in biases):
+        bcat = biases[0].detach() if len(biases) == 1 else torch.cat([b.detach() for b in biases])
+        if m.rows != n_real:
+            if m.bias is None:
+                m.bias = torch.zeros(m.rows, dtype=torch.float32, device=m.q.device)
+            m.bias[:n_real].copy_(bcat)
+        elif m.bias is None or len(biases) == 1:
+            m.bias = bcat
         else:
-            bias = None
-    _MX_WEIGHTS[key] = (vers, _WEIGHTS_EPOCH[0], m, bias, [w.detach() for w in weights], [weakref.ref(w) for w in weights])
-    return m, bias
+            m.bias.copy_(bcat)
+    elif biases is not None and any(b is not None for b in biases):
+        raise RuntimeError("linear (mx): either every weight segment has a bias or none")
+    else:
+        m.bias = None
+
+
+# the MX weights (hint of get() = the padded row count or None), cached until a segment or a bias is rewritten: weight_cache.py
+_MX_WEIGHTS = DerivedWeights(_mx_build, _mx_refresh, fits=_codes_fit, bias_versions=True)
+mx_cache_clear = _MX_WEIGHTS.clear
 
 
 def mx_stream_bf16():
@@ -322,12 +306,12 @@ def _linear_fwd_mx(x, x2, M, K, lead, weights, biases, n_out, act, residual, out
     """out: "f32" -> fp32 tensor, "mx" -> MxRows of the result (no fp32 copy), "bf16" -> bfloat16 tensor."""
     n_real = n_out
     n_out = (n_out + MX_K_MULTIPLE - 1) // MX_K_MULTIPLE * MX_K_MULTIPLE      # (a padded head: see _mx_pad_eligible)
-    wm, bias = _mx_weights(weights, biases, n_out if n_out != n_real else None)
+    wm = _MX_WEIGHTS.get(weights, biases, n_out if n_out != n_real else None)
     xm = _mx_of(x, x2, M, K, lead)
     a = N.LinearMxArgs()
     a.A, a.lda, a.a_scales, a.a_srows = xm.q.data_ptr(), K, xm.s.data_ptr(), xm.srows
     a.W, a.ldw, a.w_scales, a.w_srows = wm.q.data_ptr(), K, wm.s.data_ptr(), wm.srows
-    a.bias = N.dev_f32(bias, "linear bias") if bias is not None else None
+    a.bias = N.dev_f32(wm.bias, "linear bias") if wm.bias is not None else None
     if residual is not None:
         if residual.dtype == torch.bfloat16:            # the MX mode's bf16 residual stream
             a.residual_bf16, a.ldr16 = residual.data_ptr(), n_out
@@ -376,58 +360,43 @@ def linear_fwd(x, weights, biases, act=None, residual=None, want_preact=False, d
     want_pre_any = want_preact or want_act_grad
     mx_ok = N.mx_enabled() and (mx_eligible(K, n_out, act, drop_p, want_pre_any, biases)
                                 or _mx_pad_eligible(K, n_out, act, drop_p, want_pre_any, biases, residual, out))
-    if isinstance(x, MxRows) or (mx_ok and x.is_cuda):
-        if not mx_ok:
-            raise RuntimeError("linear: an MX input needs an MX-eligible linear (K, N multiples of 128, no dropout)")
-        for w in weights:
-            if w.shape != (seg_n, K) or not w.is_contiguous():
-                raise RuntimeError("linear: weight segments must be contiguous and equally shaped")
-        if isinstance(x, MxRows):
-            x2, M, lead = None, x.rows, x.lead
-        else:
-            x2, _, lead = _row_view(x, K)
-            M = x2.shape[0]
-        if residual is not None:
-            residual = _contig(residual)
-            if residual.numel() != M * n_out:
-                raise RuntimeError("linear: residual shape mismatch")
+    use_mx = isinstance(x, MxRows) or (mx_ok and x.is_cuda)
+    if use_mx and not mx_ok:
+        raise RuntimeError("linear: an MX input needs an MX-eligible linear (K, N multiples of 128, no dropout)")
+    for w in weights:
+        if w.shape != (seg_n, K) or not w.is_contiguous():
+            raise RuntimeError("linear: weight segments must be contiguous and equally shaped")
+    if isinstance(x, MxRows):
+        x2, lda, lead, M = None, K, x.lead, x.rows
+    else:
+        x2, lda, lead = _row_view(x, K)
+        M = x2.shape[0]
+    if residual is not None:
+        residual = _contig(residual)
+        if residual.numel() != M * n_out:
+            raise RuntimeError("linear: residual shape mismatch")
+    if use_mx:
         return _linear_fwd_mx(x, x2, M, K, lead, weights, biases, n_out, act, residual, out), None
-    x2, lda, lead = _row_view(x, K)
-    M = x2.shape[0]
     ldc = n_out
-    if pad_cols and n_out % 4 != 0 and len(lead) == 1 and residual is None and not (want_preact or want_act_grad) \
-            and drop_p == 0.0:
-        ldc = (n_out + 3) // 4 * 4
+    if pad_cols and n_out % 4 != 0 and len(lead) == 1 and residual is None and not want_pre_any and drop_p == 0.0:
+        ldc = align4(n_out)
         y = torch.empty(lead + (ldc,), dtype=torch.float32, device=x.device)[:, :n_out]
     else:
         y = torch.empty(lead + (n_out,), dtype=torch.float32, device=x.device)
-    pre = torch.empty_like(y) if (want_preact or want_act_grad) else None
+    pre = torch.empty_like(y) if want_pre_any else None
     if N.fp8_enabled() and _fp8_eligible(x2, K, n_out, biases):
-        for w in weights:
-            if w.shape != (seg_n, K) or not w.is_contiguous():
-                raise RuntimeError("linear: weight segments must be contiguous and equally shaped")
-        if residual is not None:
-            residual = _contig(residual)
-            if residual.numel() != M * n_out:
-                raise RuntimeError("linear: residual shape mismatch")
         _linear_fwd_fp8(x, x2, M, K, weights, biases, n_out, y, ldc, act, residual, pre, want_act_grad, drop_p, seed)
         return y, pre
     a = N.LinearArgs()
     a.M, a.K, a.nseg, a.seg_n = M, K, nseg, seg_n
     a.A, a.lda = N.dev_f32(x2, "linear input"), lda
     for s in range(nseg):
-        w = weights[s]
-        if w.shape != (seg_n, K) or not w.is_contiguous():
-            raise RuntimeError("linear: weight segments must be contiguous and equally shaped")
-        a.W[s] = N.dev_f32(w, "linear weight")
+        a.W[s] = N.dev_f32(weights[s], "linear weight")
         b = biases[s] if biases is not None else None
         a.bias[s] = N.dev_f32(b, "linear bias") if b is not None else None
     a.ldw = K
     a.C, a.ldc = y.data_ptr(), ldc
     if residual is not None:
-        residual = _contig(residual)
-        if residual.numel() != M * n_out:
-            raise RuntimeError("linear: residual shape mismatch")
         a.residual, a.ldr = N.dev_f32(residual, "linear residual"), n_out
     if pre is not None and want_act_grad:
         a.act_grad, a.ldg = pre.data_ptr(), n_out
@@ -476,6 +445,40 @@ def linear_bwd_input(dy, weights, in_features, residual=None, mul=None):
     return dx
 
 
+def align4(n):
+    """n floats rounded up to a multiple of 16 bytes."""
+    return (n + 3) // 4 * 4
+
+
+def wgrad_targets(nseg, seg_n, K, want_bias, dw_out, db_out, device):
+    """Where a weight-gradient launch ADDS its results: (list dW [seg_n, K], list db [seg_n] or None where want_bias[s] is
+    false). dw_out / db_out: per-segment targets or None; the targets not given are 16-byte-aligned slices of ONE
+    zero-filled buffer allocated here (one fill launch instead of two per segment)."""
+    dw_out = dw_out if dw_out is not None else [None] * nseg
+    db_out = db_out if db_out is not None else [None] * nseg
+    wsz, bsz = align4(seg_n * K), align4(seg_n)
+    need = sum(wsz for s in range(nseg) if dw_out[s] is None) + \
+        sum(bsz for s in range(nseg) if want_bias[s] and db_out[s] is None)
+    flat = torch.zeros(need, dtype=torch.float32, device=device) if need else None
+    dws, dbs, off = [], [], 0
+    for s in range(nseg):
+        dw = dw_out[s]
+        if dw is None:
+            dw = flat[off:off + seg_n * K].view(seg_n, K)
+            off += wsz
+        elif dw.shape != (seg_n, K) or not dw.is_contiguous():
+            raise RuntimeError("linear_bwd_weight: gradient target must be a contiguous [seg_n, K] tensor")
+        db = None
+        if want_bias[s]:
+            db = db_out[s]
+            if db is None:
+                db = flat[off:off + seg_n]
+                off += bsz
+        dws.append(dw)
+        dbs.append(db)
+    return dws, dbs
+
+
 def linear_bwd_weight(dy, x, nseg, seg_n, want_bias, dw_out=None, db_out=None):
     """Per segment: dW_s = dY[:, s]^T @ X and db_s = colsum(dY[:, s]) in one call.
     Returns (list dW, list db-or-None). The split-K kernel ADDS into its targets with atomics. dw_out / db_out:
@@ -496,30 +499,10 @@ def linear_bwd_weight(dy, x, nseg, seg_n, want_bias, dw_out=None, db_out=None):
     a.dY, a.ldy = N.dev_f32(dy, "linear grad_output"), ldy
     a.X, a.ldx = N.dev_f32(x2, "linear input"), ldx
     a.ldw, a.accumulate = K, 1
-    wsz, bsz = (seg_n * K + 3) // 4 * 4, (seg_n + 3) // 4 * 4          # every slice stays 16-byte aligned
-    dw_out = dw_out if dw_out is not None else [None] * nseg
-    db_out = db_out if db_out is not None else [None] * nseg
-    need = sum(wsz for s in range(nseg) if dw_out[s] is None) + \
-        sum(bsz for s in range(nseg) if want_bias[s] and db_out[s] is None)
-    flat = torch.zeros(need, dtype=torch.float32, device=dy.device) if need else None
-    dws, dbs, off = [], [], 0
+    dws, dbs = wgrad_targets(nseg, seg_n, K, want_bias, dw_out, db_out, dy.device)
     for s in range(nseg):
-        dw = dw_out[s]
-        if dw is None:
-            dw = flat[off:off + seg_n * K].view(seg_n, K)
-            off += wsz
-        elif dw.shape != (seg_n, K) or not dw.is_contiguous():
-            raise RuntimeError("linear_bwd_weight: gradient target must be a contiguous [seg_n, K] tensor")
-        db = None
-        if want_bias[s]:
-            db = db_out[s]
-            if db is None:
-                db = flat[off:off + seg_n]
-                off += bsz
-        a.dW[s] = dw.data_ptr()
-        a.dbias[s] = db.data_ptr() if db is not None else None
-        dws.append(dw)
-        dbs.append(db)
+        a.dW[s] = dws[s].data_ptr()
+        a.dbias[s] = dbs[s].data_ptr() if dbs[s] is not None else None
     _timed(lambda: N.check(N.lib().vb_linear_bwd_weight(N.stream_ptr(), ctypes.byref(a)), "vb_linear_bwd_weight"),
            2.0 * M * nseg * seg_n * K, ("wgrad", M, seg_n, K, nseg))
     return dws, dbs
@@ -550,7 +533,6 @@ def layernorm_fwd(x, gamma, beta, eps, x2=None, want_stats=False):
     x = _contig(x)
     rows, cols = _rows(x)
     y = torch.empty_like(x)
-    mean = rstd = None
     if x.dtype == torch.bfloat16:
         # the MX mode's bf16 residual stream: bf16 pre-LayerNorm sum in, bf16 row + MX codes out
         if not (N.mx_enabled() and not want_stats and x2 is None and cols % MX_K_MULTIPLE == 0 and x.is_cuda):
@@ -561,45 +543,33 @@ def layernorm_fwd(x, gamma, beta, eps, x2=None, want_stats=False):
             eps, y.data_ptr(), m.q.data_ptr(), cols, m.s.data_ptr(), m.srows), "vb_layernorm_fwd_mx16")
         y._vb_mx = (m, y._version)
         return y, None, None
-    if N.mx_enabled() and not want_stats and not torch.is_grad_enabled() and cols % MX_K_MULTIPLE == 0 and x.is_cuda:
-        # inference in the MX mode: the LayerNorm kernel also emits its output rows as MX codes + scale words
-        if x2 is not None:
-            x2 = _contig(x2)
-            if x2.shape != x.shape:
-                raise RuntimeError("layernorm: x2 shape mismatch")
-        m = MxRows(rows, cols, x.device, tuple(x.shape[:-1]))
-        N.check(N.lib().vb_layernorm_fwd_mx(
-            N.stream_ptr(), rows, cols, N.dev_f32(x, "layernorm input"), N.dev_f32(x2, "layernorm x2"),
-            N.dev_f32(gamma, "layernorm weight"), N.dev_f32(beta, "layernorm bias"), eps, y.data_ptr(), m.q.data_ptr(),
-            cols, m.s.data_ptr(), m.srows), "vb_layernorm_fwd_mx")
-        y._vb_mx = (m, y._version)
-        return y, None, None
-    if N.fp8_enabled() and not want_stats and not torch.is_grad_enabled() and cols % FP8_K_MULTIPLE == 0 and x.is_cuda:
-        # inference in fp8 mode: the LayerNorm kernel also emits the e4m3 codes of its output rows; the linears that
-        # consume this very tensor (same object, not modified since) skip their quantiser pass
-        if x2 is not None:
-            x2 = _contig(x2)
-            if x2.shape != x.shape:
-                raise RuntimeError("layernorm: x2 shape mismatch")
-        q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
-        sc = torch.empty((rows,), dtype=torch.float32, device=x.device)
-        N.check(N.lib().vb_layernorm_fwd_fp8(
-            N.stream_ptr(), rows, cols, N.dev_f32(x, "layernorm input"), N.dev_f32(x2, "layernorm x2"),
-            N.dev_f32(gamma, "layernorm weight"), N.dev_f32(beta, "layernorm bias"), eps, y.data_ptr(), q.data_ptr(),
-            cols, sc.data_ptr()), "vb_layernorm_fwd_fp8")
-        y._vb_fp8 = (q, sc, y._version)
-        return y, None, None
-    if want_stats:
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
     if x2 is not None:
         x2 = _contig(x2)
         if x2.shape != x.shape:
             raise RuntimeError("layernorm: x2 shape mismatch")
-    N.check(N.lib().vb_layernorm_fwd(
-        N.stream_ptr(), rows, cols, N.dev_f32(x, "layernorm input"), N.dev_f32(x2, "layernorm x2"),
-        N.dev_f32(gamma, "layernorm weight"), N.dev_f32(beta, "layernorm bias"), eps, y.data_ptr(),
-        mean.data_ptr() if want_stats else None, rstd.data_ptr() if want_stats else None), "vb_layernorm_fwd")
+    head = (N.stream_ptr(), rows, cols, N.dev_f32(x, "layernorm input"), N.dev_f32(x2, "layernorm x2"),
+            N.dev_f32(gamma, "layernorm weight"), N.dev_f32(beta, "layernorm bias"), eps, y.data_ptr())
+    codes = not want_stats and not torch.is_grad_enabled() and x.is_cuda
+    if codes and N.mx_enabled() and cols % MX_K_MULTIPLE == 0:
+        # inference in the MX mode: the LayerNorm kernel also emits its output rows as MX codes + scale words
+        m = MxRows(rows, cols, x.device, tuple(x.shape[:-1]))
+        N.check(N.lib().vb_layernorm_fwd_mx(*head, m.q.data_ptr(), cols, m.s.data_ptr(), m.srows), "vb_layernorm_fwd_mx")
+        y._vb_mx = (m, y._version)
+        return y, None, None
+    if codes and N.fp8_enabled() and cols % FP8_K_MULTIPLE == 0:
+        # inference in fp8 mode: the LayerNorm kernel also emits the e4m3 codes of its output rows; the linears that
+        # consume this very tensor (same object, not modified since) skip their quantiser pass
+        q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
+        sc = torch.empty((rows,), dtype=torch.float32, device=x.device)
+        N.check(N.lib().vb_layernorm_fwd_fp8(*head, q.data_ptr(), cols, sc.data_ptr()), "vb_layernorm_fwd_fp8")
+        y._vb_fp8 = (q, sc, y._version)
+        return y, None, None
+    mean = rstd = None
+    if want_stats:
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    N.check(N.lib().vb_layernorm_fwd(*head, mean.data_ptr() if want_stats else None,
+                                     rstd.data_ptr() if want_stats else None), "vb_layernorm_fwd")
     return y, mean, rstd
 
 
@@ -611,24 +581,17 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, dgamma=None, dbeta=None, drop=None):
     dy, x = _contig(dy), _contig(x)
     rows, cols = _rows(x)
     dx = torch.empty_like(x)
-    if drop is not None and drop[0] > 0.0 and cols <= 4096:
-        dgamma = dgamma if dgamma is not None else torch.empty(cols, dtype=torch.float32, device=x.device)
-        dbeta = dbeta if dbeta is not None else torch.empty(cols, dtype=torch.float32, device=x.device)
-        ws = torch.empty(N.lib().vb_layernorm_bwd_workspace(rows, cols), dtype=torch.float32, device=x.device)
-        dxd = torch.empty_like(x)
-        N.check(N.lib().vb_layernorm_bwd_drop(
-            N.stream_ptr(), rows, cols, N.dev_f32(dy, "layernorm grad_output"), N.dev_f32(x, "layernorm input"),
-            N.dev_f32(mean, "layernorm mean"), N.dev_f32(rstd, "layernorm rstd"), N.dev_f32(gamma, "layernorm weight"),
-            dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), dxd.data_ptr(), drop[0], drop[1]),
-            "vb_layernorm_bwd_drop")
-        return dx, dgamma, dbeta, dxd
     dgamma = dgamma if dgamma is not None else torch.empty(cols, dtype=torch.float32, device=x.device)
     dbeta = dbeta if dbeta is not None else torch.empty(cols, dtype=torch.float32, device=x.device)
     ws = torch.empty(N.lib().vb_layernorm_bwd_workspace(rows, cols), dtype=torch.float32, device=x.device)
-    N.check(N.lib().vb_layernorm_bwd(
-        N.stream_ptr(), rows, cols, N.dev_f32(dy, "layernorm grad_output"), N.dev_f32(x, "layernorm input"),
-        N.dev_f32(mean, "layernorm mean"), N.dev_f32(rstd, "layernorm rstd"), N.dev_f32(gamma, "layernorm weight"),
-        dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr()), "vb_layernorm_bwd")
+    head = (N.stream_ptr(), rows, cols, N.dev_f32(dy, "layernorm grad_output"), N.dev_f32(x, "layernorm input"),
+            N.dev_f32(mean, "layernorm mean"), N.dev_f32(rstd, "layernorm rstd"), N.dev_f32(gamma, "layernorm weight"),
+            dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr())
+    if drop is not None and drop[0] > 0.0 and cols <= 4096:
+        dxd = torch.empty_like(x)
+        N.check(N.lib().vb_layernorm_bwd_drop(*head, dxd.data_ptr(), drop[0], drop[1]), "vb_layernorm_bwd_drop")
+        return dx, dgamma, dbeta, dxd
+    N.check(N.lib().vb_layernorm_bwd(*head), "vb_layernorm_bwd")
     return dx, dgamma, dbeta
 
 
@@ -726,16 +689,21 @@ def additive_mask(mask):
     return out
 
 
-def _attn_args(q, k, v, mask_add, heads, drop_p, seed, dev=N.dev_f32):
-    """AttentionArgs of one launch; dev: the pointer checker of q / k / v (N.dev_f32, or ops16.dev_bf16 on the bf16 path)."""
+def _data_ptr(t, what):
+    return t.data_ptr()
+
+
+def _attn_args(q, k, v, mask_add, heads, drop_p, seed, dev=N.dev_f32, struct=N.AttentionArgs, who="attention"):
+    """Argument struct of one attention launch; dev: the pointer checker of q / k / v (N.dev_f32, or ops16.dev_bf16 on the
+    bf16 path); struct: N.AttentionArgs, or N.AttentionMxArgs (no dropout fields: drop_p / seed are not set there)."""
     Bq, Sq, H = q.shape
     Bk, Sk, _ = k.shape
     B = max(Bq, Bk)
     d = H // heads
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise RuntimeError("attention: %s must be a row-strided view" % nm)
-    a = N.AttentionArgs()
+            raise RuntimeError("%s: %s must be a row-strided view" % (who, nm))
+    a = struct()
     a.batch, a.heads, a.head_dim, a.n_q, a.n_k = B, heads, d, Sq, Sk
     a.q_batch, a.kv_batch = Bq, Bk
     a.Q, a.ldq = dev(q, "attention q"), q.stride(1)
@@ -749,7 +717,8 @@ def _attn_args(q, k, v, mask_add, heads, drop_p, seed, dev=N.dev_f32):
         a.mask_add = N.dev_f32(mask_add, "attention mask")
         keep.append(mask_add)
     a.scale = 1.0 / math.sqrt(d)
-    a.dropout_p, a.seed = float(drop_p), int(seed)
+    if struct is N.AttentionArgs:
+        a.dropout_p, a.seed = float(drop_p), int(seed)
     return a, keep, (B, Sq, Sk, H)
 
 
@@ -878,27 +847,10 @@ def attention_fwd_mx_any(q, k, v, mask_add, heads):
 def attention_fwd_mx(q, k, v, mask_add, heads):
     """q [Bq, Sq, H], k / v [Bk, Sk, H]: bfloat16 row-strided views (column slices of a fused projection); returns the
     context [B, Sq, H] as MxRows (the codes the output projection consumes)."""
-    Bq, Sq, H = q.shape
-    Bk, Sk, _ = k.shape
-    B = max(Bq, Bk)
-    d = H // heads
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if t.dtype != torch.bfloat16 or not t.is_cuda:
             raise RuntimeError("attention (mx): %s must be a bfloat16 tensor on a HIP device" % nm)
-        if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
-            raise RuntimeError("attention (mx): %s must be a row-strided view" % nm)
-    a = N.AttentionMxArgs()
-    a.batch, a.heads, a.head_dim, a.n_q, a.n_k = B, heads, d, Sq, Sk
-    a.q_batch, a.kv_batch = Bq, Bk
-    a.Q, a.ldq = q.data_ptr(), q.stride(1)
-    a.K, a.ldk = k.data_ptr(), k.stride(1)
-    a.V, a.ldv = v.data_ptr(), v.stride(1)
-    if mask_add is not None:
-        mask_add = _contig(mask_add)
-        if mask_add.numel() != Bk * Sk:
-            raise RuntimeError("attention: mask must hold %d x %d values" % (Bk, Sk))
-        a.mask_add = N.dev_f32(mask_add, "attention mask")
-    a.scale = 1.0 / math.sqrt(d)
+    a, keep, (B, Sq, Sk, H) = _attn_args(q, k, v, mask_add, heads, 0.0, 0, _data_ptr, N.AttentionMxArgs, "attention (mx)")
     out = MxRows(B * Sq, H, q.device, (B, Sq))
     a.Oq, a.ldo, a.o_scales, a.o_srows = out.q.data_ptr(), H, out.s.data_ptr(), out.srows
     N.check(N.lib().vb_attention_fwd_mx(N.stream_ptr(), ctypes.byref(a)), "vb_attention_fwd_mx")

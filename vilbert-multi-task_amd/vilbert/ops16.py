@@ -10,12 +10,12 @@ captured graphs keep their addresses).
 """
 import ctypes
 import os
-import weakref
 
 import torch
 
 from . import _native as N
 from . import ops
+from .weight_cache import DerivedWeights
 
 BF16 = torch.bfloat16
 _WEIGHTS_EPOCH = N.WEIGHTS_EPOCH
@@ -56,29 +56,29 @@ def eligible(K, n_out, seg_n=None, act=None):
     return K % 128 == 0 and n_out % 128 == 0 and seg_n % 256 == 0 and act in (None, "none", "gelu", "relu")
 
 
-class _Shadow(object):
-    """bf16 copies of one (stacked) weight: w16 [N, K] row-major for the forward, wt16 [K, N] for the input gradient."""
-    __slots__ = ("w16", "wt16", "wrefs", "keep", "vers", "epoch", "seg_n", "K", "nseg")
+def _shadow_build(weights, _biases, _hint):
+    """(w16 [N, K] row-major for the forward, wt16 [K, N] for the input gradient): bf16 copies of one (stacked) weight."""
+    w0, nseg = weights[0], len(weights)
+    seg_n, K = w0.shape
+    for w in weights:
+        if w.shape != (seg_n, K) or not w.is_contiguous():
+            raise RuntimeError("linear (bf16): weight segments must be contiguous and equally shaped")
+    if seg_n % 64 != 0 or K % 64 != 0:
+        raise RuntimeError("linear (bf16): weight dimensions must be multiples of 64")
+    pair = (torch.empty((nseg * seg_n, K), dtype=BF16, device=w0.device),
+            torch.empty((K, nseg * seg_n), dtype=BF16, device=w0.device))
+    _shadow_refresh(pair, weights, None)
+    return pair
 
 
-# (id(first weight tensor), number of stacked segments) -> _Shadow. "table": the device table of vb_weight_shadow_multi over every live entry of a device
-# (rebuilt when an entry is added or dropped); "epoch": the _native.WEIGHTS_EPOCH the shadows of that device were last
-# refreshed at by the one-launch refresh.
-_SHADOWS = {}
-_TABLES = {}
-
-
-def shadow_cache_clear():
-    _SHADOWS.clear()
-    _TABLES.clear()
-
-
-def _refresh_one(e, weights):
-    n = e.seg_n * e.nseg
+def _shadow_refresh(pair, weights, _biases):
+    w16, wt16 = pair
+    n, K = w16.shape
+    seg_n = n // len(weights)
     for s, w in enumerate(weights):
         N.check(N.lib().vb_weight_shadow_bf16(
-            N.stream_ptr(), e.seg_n, e.K, N.dev_f32(w.detach(), "linear weight"), e.K, e.w16.data_ptr() + 2 * s * e.seg_n * e.K,
-            e.K, e.wt16.data_ptr() + 2 * s * e.seg_n, n), "vb_weight_shadow_bf16")
+            N.stream_ptr(), seg_n, K, N.dev_f32(w.detach(), "linear weight"), K, w16.data_ptr() + 2 * s * seg_n * K,
+            K, wt16.data_ptr() + 2 * s * seg_n, n), "vb_weight_shadow_bf16")
 
 
 def _refresh_all(device):
@@ -87,21 +87,22 @@ def _refresh_all(device):
     import numpy as np
     dev_key = device.index
     t = _TABLES.get(dev_key)
-    live = [(k, e) for k, e in _SHADOWS.items() if e.w16.device.index == dev_key and all(r() is not None for r in e.wrefs)]
+    mine = _SHADOWS.entries(device)
+    live = [(k, e) for k, e in mine if e.alive()]
     sig = tuple(k for k, _ in live)
     if t is None or t["sig"] != sig:
-        for k in [k for k, e in _SHADOWS.items() if e.w16.device.index == dev_key and any(r() is None for r in e.wrefs)]:
-            del _SHADOWS[k]                       # (weights whose model is gone)
+        _SHADOWS.drop([k for k, e in mine if not e.alive()])      # (weights whose model is gone)
         rec = np.dtype([("w", "<u8"), ("w16", "<u8"), ("wt16", "<u8"), ("rows", "<i4"), ("cols", "<i4"), ("ld16", "<i8"),
                         ("ldt", "<i8"), ("tile0", "<i8")])
         rows, tile0 = [], 0
         for _k, e in live:
-            n = e.seg_n * e.nseg
+            w16, wt16 = e.payload
+            n, K = w16.shape
+            seg_n = n // len(e.wrefs)
             for s_, r in enumerate(e.wrefs):
-                w = r()
-                rows.append((w.data_ptr(), e.w16.data_ptr() + 2 * s_ * e.seg_n * e.K, e.wt16.data_ptr() + 2 * s_ * e.seg_n,
-                             e.seg_n, e.K, e.K, n, tile0))
-                tile0 += (e.seg_n // 64) * (e.K // 64)
+                rows.append((r().data_ptr(), w16.data_ptr() + 2 * s_ * seg_n * K, wt16.data_ptr() + 2 * s_ * seg_n,
+                             seg_n, K, K, n, tile0))
+                tile0 += (seg_n // 64) * (K // 64)
         host = np.array(rows, dtype=rec)
         dev_tab = torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).to(device)
         t = _TABLES[dev_key] = {"sig": sig, "tab": dev_tab, "n": len(rows), "tiles": tile0,
@@ -111,69 +112,35 @@ def _refresh_all(device):
         return _refresh_all(device)
     if t["n"]:
         N.check(N.lib().vb_weight_shadow_multi(N.stream_ptr(), t["n"], t["tab"].data_ptr(), t["tiles"]), "vb_weight_shadow_multi")
-    ep = _WEIGHTS_EPOCH[0]
-    t["epoch"] = ep
-    for _k, e in live:
-        e.epoch = ep
-        e.vers = tuple(r()._version for r in e.wrefs)
+    t["epoch"] = _SHADOWS.stamp([e for _k, e in live])
+
+
+# The shadows (weight_cache.py), keyed by (id(first weight tensor), number of stacked segments); a bump of the native
+# optimizer's epoch refreshes ALL registered shadows of the device with one launch at the next call (an entry registered after
+# the table was built, and not live in it, falls back to its own refresh). _TABLES: per device, the table of
+# vb_weight_shadow_multi over every live entry (rebuilt when an entry is added or dropped) and "epoch", the
+# _native.WEIGHTS_EPOCH the shadows of that device were last refreshed at by the one-launch refresh.
+_SHADOWS = DerivedWeights(_shadow_build, _shadow_refresh, on_epoch=_refresh_all)
+_TABLES = {}
+# shadows(weights) -> (W16 [N, K] bf16, Wt16 [K, N] bf16) of the stacked segments, cached until a segment is rewritten
+shadows = _SHADOWS.get
+
+
+def shadow_cache_clear():
+    _SHADOWS.clear()
+    _TABLES.clear()
 
 
 def refresh_stale(device):
     """Start of a model forward (BertModel.forward, on the stream the text / image branches fork from): when the weights
     epoch moved since the shadows of `device` were refreshed - an optimizer stepped - refresh all of them now, with the one
     launch over the device table (built here, eagerly, so that it never is built inside a stream capture or a branch)."""
-    ep = _WEIGHTS_EPOCH[0]
     t = _TABLES.get(device.index)
-    if t is not None and t.get("epoch") == ep:
+    if t is not None and t.get("epoch") == _WEIGHTS_EPOCH[0]:
         return
-    if not any(e.w16.device.index == device.index for e in _SHADOWS.values()):
-        return
-    with torch.no_grad():
-        _refresh_all(device)
-
-
-def shadows(weights, biases=None):
-    """(W16 [N, K] bf16, Wt16 [K, N] bf16) of the stacked segments, cached until a segment is rewritten: torch's version
-    counters are compared per call; a bump of the native optimizer's epoch (`_native.weights_changed()`: parameters
-    rewritten through raw pointers) refreshes ALL registered shadows of the device with one launch at the next call."""
-    w0 = weights[0]
-    nseg = len(weights)
-    key = (id(w0), nseg)
-    e = _SHADOWS.get(key)
-    if e is not None and any(r() is not w for r, w in zip(e.wrefs, weights)):
-        e = None                                   # a recycled id
-    if e is None:
-        seg_n, K = w0.shape
-        for w in weights:
-            if w.shape != (seg_n, K) or not w.is_contiguous():
-                raise RuntimeError("linear (bf16): weight segments must be contiguous and equally shaped")
-        if seg_n % 64 != 0 or K % 64 != 0:
-            raise RuntimeError("linear (bf16): weight dimensions must be multiples of 64")
-        e = _Shadow()
-        e.seg_n, e.K, e.nseg = seg_n, K, nseg
-        e.w16 = torch.empty((nseg * seg_n, K), dtype=BF16, device=w0.device)
-        e.wt16 = torch.empty((K, nseg * seg_n), dtype=BF16, device=w0.device)
-        e.wrefs = [weakref.ref(w) for w in weights]
-        e.keep = [w.detach() for w in weights]   # an alias of every segment: its address cannot be recycled under the entry
+    if _SHADOWS.entries(device):
         with torch.no_grad():
-            _refresh_one(e, weights)
-        e.vers, e.epoch = tuple(w._version for w in weights), _WEIGHTS_EPOCH[0]
-        _SHADOWS[key] = e
-        return e.w16, e.wt16
-    if e.epoch != _WEIGHTS_EPOCH[0]:
-        with torch.no_grad():
-            _refresh_all(w0.device)
-        if e.epoch != _WEIGHTS_EPOCH[0]:          # (registered after the table was built and not live in it)
-            with torch.no_grad():
-                _refresh_one(e, weights)
-            e.vers, e.epoch = tuple(w._version for w in weights), _WEIGHTS_EPOCH[0]
-        return e.w16, e.wt16
-    vers = tuple(w._version for w in weights)
-    if vers != e.vers:
-        with torch.no_grad():
-            _refresh_one(e, weights)
-        e.vers = vers
-    return e.w16, e.wt16
+            _refresh_all(device)
 
 
 def _rows2(x, K):
@@ -259,33 +226,13 @@ def linear_bwd_weight(dy, x, nseg, seg_n, want_bias, dw_out=None, db_out=None):
     M = x2.shape[0]
     if dy2.shape[0] != M:
         raise RuntimeError("linear_bwd_weight: row count mismatch")
-    dw_out = dw_out if dw_out is not None else [None] * nseg
-    db_out = db_out if db_out is not None else [None] * nseg
-    wsz, bsz = (seg_n * K + 3) // 4 * 4, (seg_n + 3) // 4 * 4
-    need = sum(wsz for s in range(nseg) if dw_out[s] is None) + \
-        sum(bsz for s in range(nseg) if want_bias[s] and db_out[s] is None)
-    flat = torch.zeros(need, dtype=torch.float32, device=dy.device) if need else None
+    dws, dbs = ops.wgrad_targets(nseg, seg_n, K, want_bias, dw_out, db_out, dy.device)
     a = N.WgradBf16Args()
     a.dY, a.ldy, a.X, a.ldx = dev_bf16(dy2, "linear grad_output"), n, dev_bf16(x2, "linear input"), K
     a.M, a.K, a.nseg, a.seg_n, a.ldw = M, K, nseg, seg_n, K
-    dws, dbs, off = [], [], 0
     for s in range(nseg):
-        dw = dw_out[s]
-        if dw is None:
-            dw = flat[off:off + seg_n * K].view(seg_n, K)
-            off += wsz
-        elif dw.shape != (seg_n, K) or not dw.is_contiguous():
-            raise RuntimeError("linear_bwd_weight: gradient target must be a contiguous [seg_n, K] tensor")
-        db = None
-        if want_bias[s]:
-            db = db_out[s]
-            if db is None:
-                db = flat[off:off + seg_n]
-                off += bsz
-        a.dW[s] = N.dev_f32(dw, "weight gradient")
-        a.dbias[s] = N.dev_f32(db, "bias gradient") if db is not None else None
-        dws.append(dw)
-        dbs.append(db)
+        a.dW[s] = N.dev_f32(dws[s], "weight gradient")
+        a.dbias[s] = N.dev_f32(dbs[s], "bias gradient") if dbs[s] is not None else None
     ops._timed(lambda: N.check(N.lib().vb_wgrad_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_wgrad_bf16"),
                2.0 * M * n * K, ("wgrad16", M, seg_n, K, nseg))
     return dws, dbs
@@ -322,24 +269,17 @@ def linear_bwd_weight_ragged(dy, x, want_bias, dw_out=None, db_out=None):
     N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), M, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
                                           dy16.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
     x16 = cast_bf16(x2)
-    dw = dw_out[0] if dw_out is not None and dw_out[0] is not None else None
-    db = db_out[0] if db_out is not None and db_out[0] is not None else None
-    if dw is None:
-        dw = torch.zeros(n, K, dtype=torch.float32, device=dy.device)
-    elif dw.shape != (n, K) or not dw.is_contiguous():
-        raise RuntimeError("linear_bwd_weight: gradient target must be a contiguous [n, K] tensor")
-    if want_bias[0] and db is None:
-        db = torch.zeros(n, dtype=torch.float32, device=dy.device)
+    dws, dbs = ops.wgrad_targets(1, n, K, want_bias, dw_out, db_out, dy.device)
     a = N.WgradBf16Args()
     a.dY, a.ldy, a.X, a.ldx = dy16.data_ptr(), n_pad, x16.data_ptr(), K
     a.M, a.K, a.nseg, a.seg_n, a.ldw, a.n_valid = M, K, 1, n_pad, K, n
-    a.dW[0] = N.dev_f32(dw, "weight gradient")
-    a.dbias[0] = N.dev_f32(db, "bias gradient") if (want_bias[0] and db is not None) else None
+    a.dW[0] = N.dev_f32(dws[0], "weight gradient")
+    a.dbias[0] = N.dev_f32(dbs[0], "bias gradient") if dbs[0] is not None else None
     ops._timed(lambda: N.check(N.lib().vb_wgrad_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_wgrad_bf16"),
                2.0 * M * n * K, ("wgrad16", M, n, K, 1))
     # (on a weight-gradient side stream the caller has made that stream torch's current one: the two bf16 temporaries come
     # from its allocator pool)
-    return [dw], [db if want_bias[0] else None]
+    return dws, dbs
 
 
 def layernorm_fwd(x, gamma, beta, eps, want_stats=False):
