@@ -157,7 +157,7 @@ def test_weight_gradient_matches_fp64(ops, v4, M, N, K, nseg):
 
 
 # ---- round 4: the tile menu of the persistent kernel (wave grid x wave tile as template parameters) ------------------------
-# configuration code WM * 1000 + TM * 100 + TM2 * 10 + TN (plan_v4 in csrc/gemm.hip), forced through the laboratory hook
+# configuration code WM * 1000 + TM * 100 + TM2 * 10 + TN (plan_v4 in csrc/gemm_plan.h), forced through the laboratory hook
 # vblab_set_gemm_v4_cfg so that every instantiation is exercised whatever the planner would choose.
 #   4544 / 4543: MIXED 320 | 256-row tiles on 8 MFMA waves - M = 320 a + 256 (32 - a): the image stream at batch 256
 #   (9472 = 20 x 320 + 12 x 256) and the other row counts of that form; N a multiple of 8 column tiles.

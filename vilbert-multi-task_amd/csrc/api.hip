@@ -1,5 +1,10 @@
-// ABI version and error strings of libvilbert_hip.so.
+// ABI version and error strings of libvilbert_hip.so; the environment helpers.
+#include <stdlib.h>
+
 #include "common.h"
+
+int vb_env_int(const char* name, int dflt) { const char* e = getenv(name); return e != nullptr ? atoi(e) : dflt; }
+double vb_env_float(const char* name, double dflt) { const char* e = getenv(name); return e != nullptr ? atof(e) : dflt; }
 
 namespace {
 const uint64_t* g_seed_epoch = nullptr;

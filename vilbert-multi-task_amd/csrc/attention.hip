@@ -941,7 +941,7 @@ int launch_bwd_fused_lds(hipStream_t st, const AttnP& p) {
 }
 
 inline bool use_lds_path(const AttnP& p) {
-    static const int on = [] { const char* e = getenv("VB_ATTN_LDS"); return e ? atoi(e) : 1; }();
+    static const int on = vb_env_int("VB_ATTN_LDS", 1);
     return on && p.n_q <= LDS_MAX_ROWS && p.n_k <= LDS_MAX_ROWS && p.q_bstride == p.n_q && p.kv_bstride == p.n_k;
 }
 
@@ -1051,7 +1051,7 @@ extern "C" int VB_ATTN_BWD(void* stream, const attn_args_t* a, const attn_grads_
     if (p.dvec_mode < VB_DVEC_COMPUTE || p.dvec_mode > VB_DVEC_GIVEN) return VB_E_BADARG;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int e = 0;
-    static const int fused = [] { const char* ev = getenv("VB_ATTN_FUSED_BWD"); return ev ? atoi(ev) : 1; }();
+    static const int fused = vb_env_int("VB_ATTN_FUSED_BWD", 1);
     if (p.dvec_mode == VB_DVEC_COMPUTE && fused && use_lds_path(p) && (gr->lddq | gr->lddk | gr->lddv) % 4 == 0) {
         // short sequences: the whole backward in one launch (K, V, Q, dO staged once)
         switch (a->head_dim) {

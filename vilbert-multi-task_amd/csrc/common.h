@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vilbert_hip.h"
+#include "gemm_plan.h"   // host-only part: the C ABI header, vb_aligned16, vb_env_int / vb_env_float
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -25,8 +25,6 @@ int text_embed_bwd_det(hipStream_t st, int batch, int n_tok, int hidden, int voc
                        const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
                        float* dpos, float* dtype, float* dtask);
 }  // namespace vbemb
-
-static inline bool vb_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

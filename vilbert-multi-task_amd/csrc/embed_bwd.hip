@@ -20,7 +20,8 @@
 //   4. one wave per tile whose first position starts a multi-run key adds that key's run sums in run order.
 // Scratch: the (device, stream) slice of the deterministic workspace; nothing is allocated, no memset, no host sync, all
 // grid sizes follow from the call's arguments (capture-safe).
-#include "gemm_core.h"
+#include "common.h"
+#include "det_workspace.h"
 
 namespace {
 
@@ -361,13 +362,13 @@ namespace vbemb {
 int text_embed_bwd_det(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
                        const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
                        float* dpos, float* dtype, float* dtask) {
-    if (!vbgemm::det_on()) return -1;
+    if (!vbdet::det_on()) return -1;
     size_t slice_bytes = 0;
-    float* slice = vbgemm::det_slice(st, &slice_bytes);
+    float* slice = vbdet::det_slice(st, &slice_bytes);
     const int r = slice != nullptr ? text_embed_bwd_ordered(st, batch, n_tok, hidden, vocab, n_types, n_tasks, ids, seg,
                                                             task_ids, dx, dword, dpos, dtype, dtask, slice, slice_bytes)
                                    : -1;
-    if (r < 0) vbgemm::det_fallback();
+    if (r < 0) vbdet::det_fallback();
     return r;
 }
 

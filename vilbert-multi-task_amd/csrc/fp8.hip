@@ -313,7 +313,7 @@ extern "C" int vb_linear_fwd_fp8(void* stream, const vb_linear_fp8_args* a) {
     Fp8X x{};
     x.A = a->A; x.lda = a->lda; x.B = a->W; x.ldb = a->ldw; x.sa = a->a_scale; x.sb = a->w_scale;
     x.nk = a->K / F8_BK;
-    static const int abl = [] { const char* e = getenv("VB_FP8_ABL"); return e ? atoi(e) : 0; }();
+    static const int abl = vb_env_int("VB_FP8_ABL", 0);
     x.abl = abl;
     if (abl == 2) x.nk = 1;
     x.n_tiles = ((p.M + 127) / 128) * p.tiles_n;

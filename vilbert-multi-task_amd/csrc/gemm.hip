@@ -31,15 +31,21 @@
 //
 // Workgroup -> tile map is XCD aware: block b runs on XCD b % 8, so XCD x gets a contiguous run
 // of logical tiles (N fastest) and the blocks sharing an A panel share one L2.
+//
+// This file, top to bottom: the round-1 kernel described above; the process-wide settings (PlanKnobs, filled from the
+// environment once); ordered split-K reduce, zero fill and the skinny weight gradient; launch_gemm - asks the planners
+// (gemm_plan.h) and launches what they chose (gemm_v2.hip, gemm_v4*.h, gemm_planes.hip, or the kernel here); the three
+// C entry points; the setters. Elsewhere: the planners (gemm_plan.h), the deterministic workspace (det_workspace.hip).
+#include <stdlib.h>
 #include <string.h>
 
-#include <mutex>
-
+#include "det_workspace.h"
 #include "gemm_v2.h"
 
 namespace {
 
 using namespace vbgemm;
+using namespace vbdet;
 
 // row-contiguous operand (global [k][ld], rows contiguous): R / 4 float4 per k row.
 template <bool VEC, int R>
@@ -252,217 +258,31 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmP p) {
     }
 }
 
+// ---- process-wide settings: this translation unit owns them and their setters (end of the file) ----------------
 unsigned long long* g_dbg = nullptr;   // lab only: where block 128 of the next v2 launches stores its cycle span
+int g_v4_last_cfg = 0;                 // plan_v4's answer for the most recent forward / dgrad launch that reached it
 
-// GEMM arithmetic mode: 0 = exact fp32 MFMA, 3 = bf16x6, 2 = bf16x3, 1 = plain bf16 (number of bf16 operand planes).
-int g_gemm_mode = -1;
-
-int gemm_mode() {
-    if (g_gemm_mode < 0) {
+// The planners' settings (gemm_plan.h), read from the environment once, on first use; the setters change them afterwards.
+PlanKnobs& plan_knobs() {
+    static PlanKnobs knobs = [] {
+        PlanKnobs k;
         const char* e = getenv("VB_GEMM_MODE");
-        g_gemm_mode = 0;
-        if (e != nullptr && !strcmp(e, "bf16x6")) g_gemm_mode = 3;
-        if (e != nullptr && !strcmp(e, "bf16x3")) g_gemm_mode = 2;
-        if (e != nullptr && !strcmp(e, "bf16")) g_gemm_mode = 1;
-    }
-    return g_gemm_mode;
-}
-
-// Tile selection of the second-generation kernel: 0 = cost model, 10 TM + TN = force a menu entry (22 | 33 | 34 | 43 |
-// 44; launches it cannot serve fall back to the round-1 kernel), -1 = round-1 kernel only. Initial value from the
-// environment (VB_GEMM_V2=0 -> -1, VB_GEMM_TILE=<code>).
-int g_gemm_tile = -2;
-
-int gemm_tile_code() {
-    if (g_gemm_tile == -2) {
-        const char* v2 = getenv("VB_GEMM_V2");
-        const char* t = getenv("VB_GEMM_TILE");
-        g_gemm_tile = (v2 != nullptr && atoi(v2) == 0) ? -1 : (t != nullptr ? atoi(t) : 0);
-    }
-    return g_gemm_tile;
-}
-
-// ---- second-generation kernel (gemm_v2.h): eligibility + tile / split plan --------------------------------------
-// Cost model: a CU retires "16 x 16 tile K-steps" at a fixed rate once its matrix pipes are saturated, the blocks of
-// a launch are dealt round-robin, so the launch takes ceil(blocks / 256) blocks of TM TN (K steps + overhead) tile
-// steps on the busiest CU; eff = measured relative main-loop efficiency of the tile shape (tools/gemm_lab).
-struct V2Plan { int tm1, tm2, tn, big_rows, small_rows, tiles_n, splits, kt_per_split; double cost; };
-
-bool aligned_ld(const void* ptr, long ld) { return ptr == nullptr || (vb_aligned16(ptr) && ld % 4 == 0); }
-
-// Modelled duration (arbitrary unit: one 16 x 16 tile K step on a saturated CU) of a launch of n1 tiles of area a1 (in
-// 16 x 16 units) followed by n2 tiles of area a2, every block running `steps` K steps, `occ` blocks resident per CU.
-// Blocks are dealt to the 256 CUs round-robin; a CU's matrix pipes are shared by its resident blocks and lose
-// efficiency when fewer than 3 blocks cover each other's barriers / prologues / epilogues (occ_eff, measured).
-double v2_launch_cost(long n1, int a1, long n2, int a2, double steps, int occ) {
-    static const double occ_eff[5] = {1.0, 0.70, 0.90, 0.97, 1.0};
-    double worst = 0.0;
-    const long q1 = n1 / 256, r1 = n1 % 256, q2 = n2 / 256, r2 = n2 % 256;
-    // the CU classes of a round-robin deal: (extra big tile?, extra small tile?)
-    for (int cls = 0; cls < 4; ++cls) {
-        const bool x1 = cls & 1, x2 = cls & 2;
-        // CUs [0, r1) hold an extra big tile; the small tiles continue the deal at CU r1: CUs [r1, r1 + r2) mod 256
-        long cnt;   // number of CUs in this class
-        const long lo2 = r1, hi2 = r1 + r2;   // extra-small range, may wrap
-        auto in2 = [&](long c) { return hi2 <= 256 ? (c >= lo2 && c < hi2) : (c >= lo2 || c < hi2 - 256); };
-        cnt = 0;
-        // count analytically would be fiddly; 256 iterations only when the class is otherwise plausible
-        for (long c = 0; c < 256; ++c) cnt += ((c < r1) == x1) && (in2(c) == x2);
-        if (cnt == 0) continue;
-        const long b1 = q1 + (x1 ? 1 : 0), b2 = q2 + (x2 ? 1 : 0);
-        long left1 = b1, left2 = b2;
-        double t = 0.0;
-        while (left1 + left2 > 0) {   // resident batches of up to occ blocks (big tiles first)
-            const long take = left1 + left2 < occ ? left1 + left2 : occ;
-            const long t1 = left1 < take ? left1 : take, t2 = take - t1;
-            t += (double)(t1 * a1 + t2 * a2) * steps / occ_eff[take];
-            left1 -= t1;
-            left2 -= t2;
-        }
-        if (t > worst) worst = t;
-    }
-    return worst;
-}
-
-template <bool A_KC, bool B_KC>
-bool plan_v2(const GemmP& p, bool vec, int splits, V2Plan& best) {
-    const int code = gemm_tile_code();
-    const bool enabled = code >= 0;
-    // forced tile: 10 TM + TN (single height) or 100 TM1 + 10 TM2 + TN (mixed heights)
-    const int forced_tm1 = code >= 100 ? code / 100 : code / 10, forced_tm2 = code >= 100 ? (code / 10) % 10 : code / 10;
-    const int forced_tn = code % 10;
-    if (!enabled || !vec || p.K % V2_BK != 0 || p.N % 4 != 0) return false;
-    if (!A_KC && p.M % 4 != 0 && p.lda < (p.M + 3) / 4 * 4) return false;
-    if (!B_KC && p.bseg % V2_BK != 0) return false;   // a K tile must not straddle two stacked weight segments
-    for (int s = 0; s < VB_MAX_SEGMENTS; ++s)
-        if (!aligned_ld(p.C[s], p.ldc) || !aligned_ld(p.bias[s], 4)) return false;
-    if (!aligned_ld(p.R, p.ldr) || !aligned_ld(p.D, p.ldd) || !aligned_ld(p.mul, p.ldmul)) return false;
-    if (B_KC && p.bseg % 4 != 0) return false;
-    constexpr bool FWD = A_KC && B_KC, DGRAD = A_KC && !B_KC;
-    const int e = p.epi;
-    const bool epi_ok = e == EPI_STORE || (FWD && (e == EPI_GELU || e == EPI_DGELU || e == EPI_RES_DROP)) ||
-                        ((FWD || DGRAD) && e == EPI_RES) || (DGRAD && (e == EPI_MUL || e == EPI_ACCUM)) ||
-                        (!A_KC && (e == EPI_ATOMIC || e == EPI_ACCUM || splits != 1)) ||
-                        (DGRAD && splits < 0 && e == EPI_ACCUM);   // split-K dgrad of a small output (vb_linear_bwd_input)
-    if (!epi_ok) return false;
-    const bool multi_seg = p.C[1] != nullptr;
-    // plans are cached per problem shape (a training step launches the same ~30 shapes thousands of times)
-    struct Key { int layout, M, N, K, cseg, splits, code; };
-    struct Entry { Key k; bool ok; V2Plan pl; };
-    static thread_local Entry cache[64];
-    static thread_local int cache_n = 0;
-    const Key key{(A_KC ? 2 : 0) + (B_KC ? 1 : 0), p.M, p.N, p.K, multi_seg ? p.cseg : 0, splits, code};
-    for (int i = 0; i < cache_n; ++i)
-        if (!memcmp(&cache[i].k, &key, sizeof(Key))) { best = cache[i].pl; return cache[i].ok; }
-
-    // {tm1, tm2, tn}: single-height tiles and the mixed-height pairs compiled in gemm_v2.hip
-    static const int menu[9][3] = {{4, 4, 4}, {3, 3, 4}, {4, 4, 3}, {3, 3, 3}, {2, 2, 2}, {4, 3, 4}, {4, 3, 3}, {3, 2, 4}, {3, 2, 3}};
-    // relative main-loop efficiency of a tile shape (tools/gemm_lab, round 2): bigger tiles move fewer bytes per FLOP
-    auto eff = [](int tm, int tn) { return tm * tn >= 16 ? 1.0 : tm * tn >= 12 ? 0.98 : tm * tn >= 9 ? 0.93 : 0.80; };
-    const int kt_total = p.K / V2_BK;
-    double best_cost = 1e300;
-    for (int c = 0; c < 9; ++c) {
-        const int tm1 = menu[c][0], tm2 = menu[c][1], tn = menu[c][2];
-        if (code > 0 && (tm1 != forced_tm1 || tm2 != forced_tm2 || tn != forced_tn)) continue;
-        if (tm1 != tm2 && splits != 1) continue;   // mixed heights: forward / dgrad only (wgrad tiles a weight matrix)
-        if (multi_seg && (tm1 != tm2 || p.cseg % (32 * tm1) != 0)) continue;   // tiles must not straddle two C row segments
-        const int bm1 = 32 * tm1, bm2 = 32 * tm2;
-        const int tiles_n = (p.N + 32 * tn - 1) / (32 * tn);
-        const int occ = (tm1 * tn <= 9 && FWD) ? 4 : 3;
-        const int max_big = tm1 == tm2 ? 0 : p.M / bm1;
-        for (int nb = 0; nb <= max_big; ++nb) {
-            // nb row tiles of the taller kind (mixed launches only), the rest of the rows in bm2-row tiles
-            const int rest = p.M - nb * bm1;
-            const int ns = tm1 == tm2 ? (p.M + bm2 - 1) / bm2 : (rest + bm2 - 1) / bm2;
-            if (tm1 != tm2 && (nb == 0 || ns == 0)) continue;
-            const long n1 = (long)nb * tiles_n, n2 = (long)ns * tiles_n;
-            const int smax = splits < 0 ? (kt_total / 4 > 0 ? (kt_total / 4 < 96 ? kt_total / 4 : 96) : 1) : 1;
-            for (int sp = 1; sp <= smax; ++sp) {
-                const int per = (kt_total + sp - 1) / sp;
-                if ((kt_total + per - 1) / per != sp) continue;
-                const double steps = per + (sp > 1 ? 3.5 : 2.0);
-                const double cost = v2_launch_cost(n1 * sp, tm1 * tn, n2 * sp, tm2 * tn, steps, occ) / eff(tm2, tn);
-                if (cost < best_cost - 1e-9) {
-                    best_cost = cost;
-                    best = {tm1, tm2, tn, nb, ns, tiles_n, sp, per, cost};
-                }
-            }
-        }
-    }
-    const bool ok = best_cost < 1e299;
-    if (cache_n < 64) cache[cache_n++] = Entry{key, ok, best};
-    return ok;
-}
-
-// Persistent one-block-per-CU kernel (gemm_v4.h): -> tile width code (3 = 96, 4 = 128 columns) or 0 = not used. Called
-// after plan_v2 accepted the launch (alignment, epilogue). Mode (vb_set_gemm_v4 / VB_GEMM_V4): 0 = never, 1 = wherever
-// its tiles fill whole rounds of the 256 CUs (default), 2 = every eligible launch (tests, lab).
-// Measured in one process on the product library (tools/gemm_lab_prod LAB_V4_AB=1, profiles/r03_gemm_lab_v4_ab*.txt):
-// +2 ... +13 % on every forward / dgrad shape of the model at M = 9216 and 18432 (137-147 TF against 120-136 for the
-// 4-wave blocks on the same box), bert_large shapes included.
-int g_gemm_v4 = -1;
-
-int gemm_v4_mode() {
-    if (g_gemm_v4 < 0) {
-        const char* e = getenv("VB_GEMM_V4");
-        g_gemm_v4 = e != nullptr ? atoi(e) : 1;
-        if (g_gemm_v4 < 0 || g_gemm_v4 > 2) g_gemm_v4 = 1;
-    }
-    return g_gemm_v4;
-}
-
-// Deterministic split-K (vb_set_deterministic): the splits of a launch store their partial products to a workspace
-// registered by the caller and splitk_reduce_kernel adds them to C in split order - bit-identical results from run to
-// run, where the default (fp32 atomics from all splits into C) depends on the order the blocks happen to finish in.
-int g_det = -1;
-// One workspace PER DEVICE (a process may drive several GPUs: nn.DataParallel replicas, the reference's non-distributed
-// multi-GPU path train_concap.py:513-515): a launch only ever uses the workspace registered for the device it runs on, and
-// falls back to the fp32-atomics split-K when there is none. Each workspace is cut into DET_SLICES equal slices; every
-// (device, stream) that issues split launches gets its own (first come, first served, for the lifetime of that
-// registration), so the text / image / weight-gradient side streams keep overlapping. A stream that comes after the
-// slices are taken, or a launch whose partials do not fit a slice, runs with atomics (correct, just not bit-reproducible)
-// and is counted (vb_deterministic_fallbacks) - it is never an error.
-constexpr int DET_SLICES = 8;
-constexpr int DET_MAX_DEV = 16;
-struct DetDevice {
-    float* ws = nullptr;
-    size_t bytes = 0;
-    hipStream_t streams[DET_SLICES];
-    int nstreams = 0;
-};
-DetDevice g_det_dev[DET_MAX_DEV];
-long g_det_fallbacks = 0;
-std::mutex g_det_mutex;     // autograd runs backward nodes on its own threads
-
-bool deterministic() {
-    if (g_det < 0) g_det = 0;
-    return g_det != 0;
-}
-
-// workspace slice of (current device, stream): base pointer + slice size, or nullptr when the device has no workspace or
-// its slices are taken
-float* det_slice_of(hipStream_t st, size_t* slice_bytes) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= DET_MAX_DEV) return nullptr;
-    std::lock_guard<std::mutex> lock(g_det_mutex);
-    DetDevice& d = g_det_dev[dev];
-    if (d.ws == nullptr) return nullptr;
-    const size_t slice = d.bytes / DET_SLICES / 16 * 16;
-    *slice_bytes = slice;
-    int k = -1;
-    for (int i = 0; i < d.nstreams; ++i)
-        if (d.streams[i] == st) { k = i; break; }
-    if (k < 0) {
-        if (d.nstreams == DET_SLICES) return nullptr;
-        d.streams[d.nstreams] = st;
-        k = d.nstreams++;
-    }
-    return d.ws + (size_t)k * (slice / sizeof(float));
-}
-
-void det_count_fallback() {
-    std::lock_guard<std::mutex> lock(g_det_mutex);
-    ++g_det_fallbacks;
+        if (e != nullptr && !strcmp(e, "bf16x6")) k.gemm_mode = 3;
+        if (e != nullptr && !strcmp(e, "bf16x3")) k.gemm_mode = 2;
+        if (e != nullptr && !strcmp(e, "bf16")) k.gemm_mode = 1;
+        k.tile_code = vb_env_int("VB_GEMM_V2", 1) == 0 ? -1 : vb_env_int("VB_GEMM_TILE", k.tile_code);
+        k.v4_mode = vb_env_int("VB_GEMM_V4", k.v4_mode);
+        if (k.v4_mode < 0 || k.v4_mode > 2) k.v4_mode = 1;
+        k.v4_force_cfg = vb_env_int("VB_GEMM_V4_CFG", k.v4_force_cfg);
+        k.v4_tn = vb_env_int("VB_GEMM_V4_TN", k.v4_tn);
+        k.v4_margin = vb_env_float("VB_GEMM_V4_MARGIN", k.v4_margin);
+        k.v4_menu = vb_env_int("VB_GEMM_V4_MENU", 1) != 0;
+        k.v4_smallm = vb_env_int("VB_GEMM_V4_SMALLM", 0) != 0;
+        k.hybrid = vb_env_int("VB_GEMM_HYBRID", k.hybrid);
+        k.wgrad_rmax = vb_env_int("VB_WGRAD_RMAX", k.wgrad_rmax);
+        return k;
+    }();
+    return knobs;
 }
 
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, const float* __restrict__ cs_ws,
@@ -511,14 +331,15 @@ int zero_rows(hipStream_t st, float* c, long ldc, int rows, int cols) {
     return 0;
 }
 
+// Deterministic split-K (vb_set_deterministic): the splits of a launch store their partial products to the stream's
+// slice of the workspace (det_workspace.hip) and splitk_reduce_kernel adds them to C in split order.
 // Points the launch at the workspace (-> the kernels store partials instead of adding atomically). false = no slice for
-// this (device, stream) or the slice is too small for `splits` partial copies of C: the caller launches with atomics.
+// this (device, stream) or the slice is too small for `splits` partial copies of C (counted): the caller launches with
+// atomics.
 bool det_prepare(hipStream_t st, GemmP& p, int splits) {
     const int cs_parts = p.det_cs_parts < 1 ? 1 : p.det_cs_parts;
-    const size_t need = ((size_t)splits * p.M * p.N + (size_t)splits * cs_parts * p.M) * sizeof(float);
-    size_t slice = 0;
-    float* base = det_slice_of(st, &slice);
-    if (base == nullptr || need > slice) { det_count_fallback(); return false; }
+    float* base = det_claim(st, ((size_t)splits * p.M * p.N + (size_t)splits * cs_parts * p.M) * sizeof(float));
+    if (base == nullptr) return false;
     p.det_cs_parts = cs_parts;
     p.det_ws = base;
     p.det_stride = (long)p.M * p.N;
@@ -612,13 +433,8 @@ int launch_wgrad_skinny(hipStream_t st, const vb_linear_bwd_weight_args* a) {
     if (a->nseg != 1 || a->K > SK_KMAX || a->M < 256 || a->seg_n % 4 != 0 || a->ldy % 4 != 0 || !vb_aligned16(a->dY)) return -1;
     float* ws = nullptr;
     const int slabs = SK_SLABS;
-    if (deterministic()) {
-        const size_t need = (size_t)slabs * (a->K + 1) * a->seg_n * sizeof(float);
-        size_t slice = 0;
-        ws = det_slice_of(st, &slice);
-        if (ws != nullptr && need > slice) ws = nullptr;
-        if (ws == nullptr) det_count_fallback();       // slabs added with fp32 atomics instead
-    }
+    // (no slice, or too small a one: counted, slabs added with fp32 atomics instead)
+    if (det_on()) ws = det_claim(st, (size_t)slabs * (a->K + 1) * a->seg_n * sizeof(float));
     const int rows_per_slab = (int)((a->M + slabs - 1) / slabs);
     hipLaunchKernelGGL(wgrad_skinny_kernel, dim3((unsigned)((a->seg_n + 255) / 256), (unsigned)slabs), dim3(256), 0, st, (int)a->M,
                        (int)a->seg_n, (int)a->K, a->dY, (long)a->ldy, a->X, (long)a->ldx, a->dW[0], (long)a->ldw, a->dbias[0], ws,
@@ -633,159 +449,30 @@ int launch_wgrad_skinny(hipStream_t st, const vb_linear_bwd_weight_args* a) {
     return 0;
 }
 
-// -> configuration code WM * 1000 + TM * 100 + TM2 * 10 + TN of the persistent kernel (gemm_v4.h, dispatch_v4 in
-// gemm_v2.hip), 0 = not used. Round 4: a tile menu instead of the two 288-row shapes -
-//   * the round-3 shapes 288 x 128 / 288 x 96 (12 MFMA waves);
-//   * MIXED 320 | 256-row tiles on 8 MFMA waves when M = 320 a + 256 (32 - a): the 37-region image stream at batch 256
-//     (M = 9472 = 20 x 320 + 12 x 256) becomes exactly 32 row tiles x N / 128 column tiles - one tile per CU and round;
-//   * small-M shapes (per-GPU batch 64: M = 2304 / 2368 rows - 64 tiles of 288 rows would leave 192 CUs idle): 192 x 128,
-//     96 x 128, 96 x 96 (12 waves), 128 x 64, 64 x 128 (8 waves).
-// Choice by a TIME model fitted to in-process A/B runs of every configuration on the model's shapes
-// (tools/lab_v4_menu.sh, profiles/r04_gemm_lab_v4_menu_*.txt): a persistent launch costs
-//     9.4 us  +  rounds x K steps x (ideal matrix-pipe time of one tile K step) / 0.94  +  (rounds - 1) x 12 us
-// (launch + prologue + epilogue are ~9.4 us whatever the tile; every configuration's K step runs at ~0.94 of the pipe;
-// an output-tile boundary inside a launch is a store burst), with the mixed launch timed by its 320-row
-// tiles; the 4-wave alternative costs 0.93 x (plan_v2's modelled cost, in 32 x 32-tile K steps of 53.4 ns). The persistent
-// kernel is taken when its modelled time is lower (mode 1), always when eligible (mode 2).
-// VB_GEMM_V4_CFG=<code> / vblab_set_gemm_v4_cfg force one configuration wherever the shape allows it (laboratory, tests).
-struct V4Opt { int wm, tm, tn; };
-int g_v4_force_cfg = -1;
-int g_v4_last_cfg = 0;
-int plan_v4(const GemmP& p, bool b_kc, double v2_cost) {
-    const int mode = gemm_v4_mode();
-    if (mode == 0) return 0;
-    if (p.K % 32 != 0 || p.C[1] != nullptr || p.epi == EPI_ATOMIC || p.epi == EPI_GENERIC || p.epi == EPI_PRE_GELU) return 0;
-    static const int force_tn = [] { const char* e = getenv("VB_GEMM_V4_TN"); return e ? atoi(e) : 0; }();
-    if (g_v4_force_cfg < 0) { const char* e = getenv("VB_GEMM_V4_CFG"); g_v4_force_cfg = e ? atoi(e) : 0; }
-    const int force_cfg = g_v4_force_cfg;
-    static const double margin = [] { const char* e = getenv("VB_GEMM_V4_MARGIN"); return e ? atof(e) : 0.98; }();
-    auto cols_ok = [&](int tn) {
-        if (p.N % (32 * tn) != 0) return false;
-        return !(b_kc && p.B[1] != nullptr && p.bseg % (32 * tn) != 0);   // a tile must not straddle two stacked weights
-    };
-    constexpr double CU_FLOPS = 157.3e12 / 256.0, T_FIXED = 9.4e-6, T_BOUNDARY = 12e-6, STEP_EFF = 0.94;
-    const double nk = p.K / 16;
-    auto model = [&](int bm, int bn, long tiles) {
-        const double rounds = (double)((tiles + 255) / 256);
-        return T_FIXED + rounds * nk * (2.0 * bm * bn * 16.0 / CU_FLOPS) / STEP_EFF + (rounds - 1.0) * T_BOUNDARY;
-    };
-    static const V4Opt menu[] = {{6, 3, 4}, {6, 3, 3}, {6, 2, 4}, {6, 1, 4}, {6, 1, 3}, {4, 2, 2}, {4, 1, 4}};
-    // VB_GEMM_V4_MENU=0: the round-3 planner (288-row shapes only, >= 0.90 fill) for A/B runs
-    static const bool menu_on = [] { const char* e = getenv("VB_GEMM_V4_MENU"); return e == nullptr || atoi(e) != 0; }();
-    double best = 1e30;
-    int best_cfg = 0;
-    bool best_fills = false;
-    for (const V4Opt& o : menu) {
-        if (!cols_ok(o.tn) || (force_tn != 0 && force_tn != o.tn)) continue;
-        const int cfg = o.wm * 1000 + o.tm * 100 + o.tn;
-        if (force_cfg != 0 && force_cfg != cfg) continue;
-        if (!menu_on && o.tm != 3) continue;
-        const int bm = 16 * o.tm * o.wm;
-        const long rows = (p.M + bm - 1) / bm, tiles = rows * (p.N / (32 * o.tn));
-        const double t = model(bm, 32 * o.tn, tiles);
-        if (t < best - 1e-12) {
-            best = t;
-            best_cfg = cfg;
-            // the round-3 rule: a 288-row shape whose launched tile slots are >= 90 % useful
-            best_fills = o.tm == 3 && (double)tiles / (double)((tiles + 255) / 256 * 256) * ((double)p.M / (rows * 288.0)) >= 0.90;
-        }
-    }
-    bool best_mixed = false;
-    // mixed 320 | 256-row tiles (8 MFMA waves): M = 320 a + 256 (32 - a), 0 < a < 32
-    for (int tn = 4; tn >= 3 && menu_on; --tn) {
-        const int cfg = 4540 + tn;
-        if (!cols_ok(tn) || (p.N / (32 * tn)) % 8 != 0 || (force_cfg != 0 && force_cfg != cfg) || (force_tn != 0 && force_tn != tn)) continue;
-        const int rest = p.M - 32 * 256;
-        if (rest <= 0 || rest % 64 != 0 || rest / 64 >= 32) continue;
-        const double t = model(320, 32 * tn, 32L * (p.N / (32 * tn)));
-        if (t < best - 1e-12) { best = t; best_cfg = cfg; best_mixed = true; best_fills = false; }
-    }
-    if (best_cfg == 0) return 0;
-    if (mode == 2 || force_cfg != 0) return best_cfg;
-    // mode 1. Measured (in-process A/B on every shape of the model, profiles/r03_gemm_lab_v4_ab_*.txt,
-    // r04_gemm_lab_v4_menu_*.txt): the 288-row shapes that fill the chip and the mixed launch beat the 4-wave blocks on
-    // every forward / dgrad shape but one (+4 ... +14 %; 9472 x 1024 x 3 x 1024 forward: -1 %). For the small-M menu the two models are compared; plan_v2's cost is in
-    // 32 x 32-tile K steps (53.4 ns on a saturated CU) and tracks the measured time (x 0.93) while a CU holds at most two
-    // 4-wave blocks - beyond that (large M, where the menu has nothing to offer anyway) it is not calibrated: 4-wave.
-    if (best_fills || best_mixed) return best_cfg;
-    // The small-M menu wins most isolated A/Bs (profiles/r04_gemm_lab_v4_menu_M2304.txt / _M2368.txt, planner's choice against the
-    // 4-wave blocks: +8 ... +20 % on 15 of 20 forward / dgrad launches, -1 ... -13 % on 5) and is a WASH inside the batch-64 training
-    // step (profiles/r04_bench_b64_menu_ab.txt: 1,986 -> 2,022 samples/s eager, 1,716 -> 1,773 single-stream, 1,887 -> 1,932 as
-    // one HIP graph on one box; 1,954 -> 1,866 on an earlier one): there the text / image / weight-gradient streams keep
-    // several kernels in flight, the 4-wave blocks of different kernels co-reside on a CU and cover each other's bubbles,
-    // while a persistent block owns its CU - so it is opt-in (VB_GEMM_V4_SMALLM=1: single-stream inference, laboratory).
-    static const bool small_m = [] { const char* e = getenv("VB_GEMM_V4_SMALLM"); return e != nullptr && atoi(e) != 0; }();
-    if (!menu_on || !small_m) return 0;
-    const long v2_tiles = (long)((p.M + 95) / 96) * ((p.N + 95) / 96);     // upper bound of plan_v2's block count
-    if (v2_tiles > 3 * 256) return 0;
-    const double t_v2 = 0.93 * 53.4e-9 * v2_cost;
-    return best < margin * t_v2 ? best_cfg : 0;
-}
-
-// Persistent weight-gradient kernel (gemm_v4w.h): 384 x 96 tiles of dW times K splits as equal work units. Fills the
-// launch fields and returns true when the shape divides (text-stream weights: 768 / 2304 / 3072 rows, 768 / 3072
-// columns) and the units fill the chip.
-int plan_v4w(GemmP& p) {
-    const int mode = gemm_v4_mode();
-    if (mode == 0 || p.K % 32 != 0) return -1;
-    // {tile rows, tile columns, relative main-loop efficiency}: 12 MFMA waves for the 384-row tiles, 8 for the 256-row ones
-    static const struct { int bm, bn; double eff; } cfgs[3] = {{384, 96, 1.0}, {256, 128, 0.95}, {256, 96, 0.93}};
-    const int kt = p.K / V2_BK;
-    double best = 1e300;
-    int best_s = 0, best_c = -1;
-    for (int c = 0; c < 3; ++c) {
-        const int BM = cfgs[c].bm, BN = cfgs[c].bn;
-        if (p.M % BM != 0 || p.N % BN != 0 || p.cseg % BM != 0) continue;
-        const long tiles = (long)(p.M / BM) * (p.N / BN);
-        for (int s = 1; s <= 64; ++s) {
-            if (kt % s != 0) continue;
-            const int nk = kt / s;
-            if (nk % 2 != 0 || nk < 8) continue;
-            const long units = tiles * s, rounds = (units + 255) / 256;
-            const double eff = (double)units / (double)(rounds * 256);
-            // measured (tools/gemm_lab_prod LAB_V4_AB=1, profiles/r03_gemm_lab_v4w_ab.txt): +8.5 % with 144 K steps per unit
-            // (W[3072, 768], W[768, 3072] at 9216 rows), -5 % with 36 (W[768, 768] needs 16 splits to fill the chip and
-            // every unit ends in a 147 KB burst of stores that all 256 blocks issue at the same instant)
-            if (mode != 2 && (eff < 0.85 || nk < 64)) continue;
-            // ~8 K steps of epilogue per unit; cost in units of one 16 x 16 tile K step per CU
-            const double cost = (double)rounds * (nk + 8.0) * (BM / 16) * (BN / 16) / cfgs[c].eff;
-            if (cost < best - 1e-9) { best = cost; best_s = s; best_c = c; }
-        }
-    }
-    if (best_c < 0) return -1;
-    const int BM = cfgs[best_c].bm, BN = cfgs[best_c].bn;
-    const long tiles = (long)(p.M / BM) * (p.N / BN);
-    p.tiles_n = p.N / BN;
-    p.n_small = (int)tiles;
-    p.n_big = (int)(tiles * best_s);
-    p.ktiles_per_split = kt / best_s;
-    p.epi = best_s > 1 ? EPI_ATOMIC : EPI_ACCUM;
-    return best_c;
-}
-
 // splits: 1 = no split-K; < 0 = split-K launch (wgrad), choose the count; legacy_splits = count for the round-1 kernel
 template <bool A_KC, bool B_KC>
 int launch_gemm(hipStream_t st, GemmP p, bool vec, int splits, int legacy_splits = 1, int vec_v2 = -1) {
-    static const int flags = [] { const char* e = getenv("VB_GEMM_FLAGS"); return e ? atoi(e) : 0; }();
+    static const int flags = vb_env_int("VB_GEMM_FLAGS", 0);
     p.flags = flags;
+    const PlanKnobs& kn = plan_knobs();
     // VB_GEMM_MODE: "f32" (default) = exact fp32 MFMA; "bf16x6" / "bf16x3" = fp32 emulated on the bf16
     // matrix cores with 3 / 2 operand planes (gemm_planes.hip)
-    const int planes = gemm_mode();
+    const int planes = kn.gemm_mode;
     V2Plan pl;
     p.dbg = g_dbg;
     // vec_v2: 16-byte loads legal for the second-generation kernel (it tolerates a row-contiguous A whose row count is
     // not a multiple of 4 when the leading dimension leaves room for the last float4); default = same as `vec`
-    if (planes == 0 && plan_v2<A_KC, B_KC>(p, vec_v2 < 0 ? vec : vec_v2 != 0, splits, pl)) {
-        const int c4w = (!A_KC && !B_KC && splits < 0) ? plan_v4w(p) : -1;
+    if (planes == 0 && plan_v2<A_KC, B_KC>(kn, p, vec_v2 < 0 ? vec : vec_v2 != 0, splits, pl)) {
+        const int c4w = (!A_KC && !B_KC && splits < 0) ? plan_v4w(kn, p) : -1;
         if (c4w >= 0) {
             const int s4 = p.n_big / p.n_small;
-            const bool det = s4 > 1 && deterministic() && det_prepare(st, p, s4);
+            const bool det = s4 > 1 && det_on() && det_prepare(st, p, s4);
             if (int e = launch_gemm_v4_tn(st, p, c4w)) return e;
             return det ? det_finish(st, p, s4) : 0;
         }
         // persistent 288-row tiles (gemm_v4.h) where they fill the chip in whole rounds
         if (A_KC && splits == 1) {
-            const int cfg4 = plan_v4(p, B_KC, pl.cost);
+            const int cfg4 = plan_v4(kn, p, B_KC, pl.cost);
             g_v4_last_cfg = cfg4;
             if (cfg4 != 0) return B_KC ? launch_gemm_v4_nt(st, p, cfg4) : launch_gemm_v4_nn(st, p, cfg4);
         }
@@ -795,7 +482,7 @@ int launch_gemm(hipStream_t st, GemmP p, bool vec, int splits, int legacy_splits
         p.m_split = pl.big_rows * 32 * pl.tm1;
         if (splits < 0) p.epi = pl.splits > 1 ? EPI_ATOMIC : EPI_ACCUM;
         const int tiles = (pl.big_rows + pl.small_rows) * pl.tiles_n;
-        const bool det = splits < 0 && pl.splits > 1 && deterministic() && det_prepare(st, p, pl.splits);
+        const bool det = splits < 0 && pl.splits > 1 && det_on() && det_prepare(st, p, pl.splits);
         int e = 0;
         if (A_KC && B_KC) e = launch_gemm_v2_nt(st, p, pl.tm1, pl.tm2, pl.tn, tiles, pl.splits);
         else if (A_KC) e = launch_gemm_v2_nn(st, p, pl.tm1, pl.tm2, pl.tn, tiles, pl.splits);
@@ -826,14 +513,14 @@ int launch_gemm(hipStream_t st, GemmP p, bool vec, int splits, int legacy_splits
         const int kt_total = (p.K + BK - 1) / BK;
         p.ktiles_per_split = (kt_total + splits - 1) / splits;
         splits = (kt_total + p.ktiles_per_split - 1) / p.ktiles_per_split;
-        if (deterministic() && splits > 1) {
+        if (det_on() && splits > 1) {
             p.det_cs_parts = planes != 0 ? 2 : 1;
             det_legacy = p.N % 4 == 0 && det_prepare(st, p, splits);
             if (!det_legacy) { splits = 1; p.ktiles_per_split = kt_total; }
         }
         p.epi = splits > 1 ? EPI_ATOMIC : EPI_ACCUM;
     }
-    plan_tiles(p, splits, planes != 0);
+    plan_tiles(kn, p, splits, planes != 0);
     dim3 grid(p.n_big + p.n_small, splits), block(256);
     if (planes != 0) {
         // operands split into bf16 planes on their way into LDS (gemm_planes.hip)
@@ -854,81 +541,18 @@ int launch_gemm(hipStream_t st, GemmP p, bool vec, int splits, int legacy_splits
     return 0;
 }
 
+// Cut of a contraction that is not a multiple of 16 (it would send the whole GEMM to the round-1 kernel with scalar
+// loads): `bulk` = its first k_main = K / 16 * 16 elements, for the second-generation kernel, `tail` = the <= 15
+// leftover ones, a tiny launch. The tail's operands start a_step / b_step floats per contraction element further on:
+// 1 for a k-contiguous operand, the leading dimension for a row-contiguous one.
+void split_ragged_k(const GemmP& p, int k_main, long a_step, long b_step, GemmP& bulk, GemmP& tail) {
+    bulk = tail = p;
+    bulk.K = k_main; bulk.bseg = k_main;
+    tail.K = p.K - k_main; tail.bseg = tail.K;
+    tail.A = p.A + k_main * a_step; tail.B[0] = p.B[0] + k_main * b_step;
+}
+
 }  // namespace
-
-// Laboratory hook (tools/gemm_lab.cpp, not part of the product ABI): device buffer of 2 x uint64 receiving
-// {shader cycles of the K loop of block 128, its K steps} of every following second-generation GEMM launch.
-extern "C" void vblab_gemm_cycles(unsigned long long* dev_buf) { g_dbg = dev_buf; }
-// Laboratory / test hook (not part of the product ABI): force one persistent-kernel configuration (plan_v4 code, 0 = the
-// planner's choice) wherever the shape allows it. Returns the previous value.
-// configuration code of the most recent forward / dgrad launch that reached the planner (0 = it ran on the 4-wave blocks)
-extern "C" int vblab_last_gemm_v4_cfg(void) { return g_v4_last_cfg; }
-extern "C" int vblab_set_gemm_v4_cfg(int cfg) {
-    const int prev = g_v4_force_cfg < 0 ? 0 : g_v4_force_cfg;
-    g_v4_force_cfg = cfg;
-    return prev;
-}
-
-extern "C" int vb_set_gemm_tile(int code) {
-    const int prev = gemm_tile_code();
-    if (code == -1 || code == 0 || code == 22 || code == 33 || code == 34 || code == 43 || code == 44 || code == 434 ||
-        code == 433 || code == 324 || code == 323)
-        g_gemm_tile = code;
-    return prev;
-}
-
-extern "C" int vb_set_deterministic(int on, void* workspace, int64_t workspace_bytes) {
-    const int prev = g_det > 0 ? 1 : 0;
-    if (on != 0 && on != 1) return prev;
-    if (on && (workspace == nullptr || workspace_bytes <= 0 || !vb_aligned16(workspace))) return VB_E_BADARG;
-    int dev = -1;
-    if (on) {
-        // the workspace serves the device it lives on, whichever device is current now
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, workspace) != hipSuccess) { (void)hipGetLastError(); return VB_E_BADARG; }
-        dev = attr.device;
-        if (dev < 0 || dev >= DET_MAX_DEV) return VB_E_BADARG;
-    }
-    std::lock_guard<std::mutex> lock(g_det_mutex);
-    if (!on) {
-        for (DetDevice& d : g_det_dev) d = DetDevice();
-        g_det = 0;
-        return prev;
-    }
-    DetDevice& d = g_det_dev[dev];
-    // re-registering the same buffer keeps the stream -> slice assignment (captured graphs have it baked in)
-    if (d.ws != static_cast<float*>(workspace) || d.bytes != (size_t)workspace_bytes) {
-        d = DetDevice();
-        d.ws = static_cast<float*>(workspace);
-        d.bytes = (size_t)workspace_bytes;
-    }
-    g_det = 1;
-    g_det_fallbacks = 0;
-    return prev;
-}
-
-namespace vbgemm {
-bool det_on() { return deterministic(); }
-float* det_slice(hipStream_t st, size_t* slice_bytes) { return det_slice_of(st, slice_bytes); }
-void det_fallback() { det_count_fallback(); }
-}  // namespace vbgemm
-
-extern "C" int64_t vb_deterministic_fallbacks(void) {
-    std::lock_guard<std::mutex> lock(g_det_mutex);
-    return (int64_t)g_det_fallbacks;
-}
-
-extern "C" int vb_set_gemm_v4(int mode) {
-    const int prev = gemm_v4_mode();
-    if (mode >= 0 && mode <= 2) g_gemm_v4 = mode;
-    return prev;
-}
-
-extern "C" int vb_set_gemm_mode(int planes) {
-    const int prev = gemm_mode();
-    if (planes >= 0 && planes <= 3) g_gemm_mode = planes;
-    return prev;
-}
 
 extern "C" int vb_linear_fwd(void* stream, const vb_linear_args* a) {
     if (a == nullptr || a->A == nullptr || a->C == nullptr) return VB_E_BADARG;
@@ -1003,9 +627,8 @@ extern "C" int vb_linear_bwd_input(void* stream, const vb_linear_bwd_input_args*
             p.epi = (p.R == nullptr && !p.accumulate) ? EPI_MUL : EPI_GENERIC;
         }
         p.ktiles_per_split = (p.K + BK - 1) / BK;
-        // A contraction length that is not a multiple of 16 (the MLM decoder: 30522 out-features) would send the whole
-        // GEMM to the round-1 kernel with scalar loads: run the aligned bulk on the second-generation kernel and
-        // add the <= 15 leftover k with a second, tiny launch.
+        // A contraction length that is not a multiple of 16 (the MLM decoder: 30522 out-features): the aligned bulk on the
+        // second-generation kernel, the <= 15 leftover k added by a second, tiny launch (split_ragged_k).
         // A small output with a long contraction (the MLM decoder: dX [1628 x 768] over 30522 out-features = 136 tiles
         // for 256 CUs, 66 TF) is cut along K as the wgrad launches are: the planner picks the split count and the splits
         // add into dX with atomics (dX is zero-filled first unless it already holds a contribution).
@@ -1017,11 +640,8 @@ extern "C" int vb_linear_bwd_input(void* stream, const vb_linear_bwd_input_args*
         auto launch_main = [&](GemmP q, bool vq) -> int {
             if (!split_k) return launch_gemm<true, false>(st, q, vq, 1);
             int planes_splits = 1;
-            if (gemm_mode() != 0) {
-                const long tiles = (long)((q.M + 127) / 128) * ((q.N + 127) / 128);
-                long sp = (768 + tiles - 1) / tiles;
-                if (sp > q.K / 1024) sp = q.K / 1024;
-                planes_splits = (int)(sp < 1 ? 1 : (sp > 32 ? 32 : sp));
+            if (plan_knobs().gemm_mode != 0) {
+                planes_splits = plan_planes_dgrad_splits(q.M, q.N, q.K);
                 if (planes_splits == 1) return launch_gemm<true, false>(st, q, vq, 1);
             }
             if (q.epi == EPI_STORE) {
@@ -1034,10 +654,10 @@ extern "C" int vb_linear_bwd_input(void* stream, const vb_linear_bwd_input_args*
         const int k_main = p.K / V2_BK * V2_BK;
         if (fused && a->nseg == 1 && k_main >= 256 && k_main != p.K && p.R == nullptr && p.mul == nullptr &&
             a->K % 4 == 0 && a->ldy % 4 == 0 && a->ldw % 4 == 0 && vb_aligned16(p.A) && vb_aligned16(p.B[0])) {
-            GemmP m = p, t = p;
-            m.K = k_main; m.bseg = k_main; m.ktiles_per_split = k_main / BK;
+            GemmP m, t;
+            split_ragged_k(p, k_main, 1, p.ldb, m, t);
+            m.ktiles_per_split = k_main / BK;
             if (int e = launch_main(m, true)) return e;
-            t.K = p.K - k_main; t.bseg = t.K; t.A = p.A + k_main; t.B[0] = p.B[0] + (long)k_main * p.ldb;
             t.accumulate = 1; t.epi = EPI_ACCUM; t.ktiles_per_split = 1;
             if (int e = launch_gemm<true, false>(st, t, false, 1)) return e;
             continue;
@@ -1086,24 +706,7 @@ extern "C" int vb_linear_bwd_weight(void* stream, const vb_linear_bwd_weight_arg
         p.act = VB_ACT_NONE; p.accumulate = 1;
         const int tiles = ((p.M + 127) / 128) * ((p.N + 127) / 128);
         const int kt_total = (p.K + BK - 1) / BK;
-        // Split count: tiles x splits workgroups should fill r whole "one block per CU" rounds of the 256
-        // CUs (all co-resident, so r = blocks per CU) WITHOUT spilling into a partial extra round.
-        // Measured: r = 4 beats fewer, longer blocks (one block per CU leaves the matrix pipe idle during
-        // every barrier / epilogue); take the largest r <= 4 that fills >= 93 % of its slots.
-        int splits = 1;
-        {
-            double best = -1.0;
-            static const int rmax = [] { const char* e = getenv("VB_WGRAD_RMAX"); return e ? atoi(e) : 4; }();
-            for (int r = rmax; r >= 2; --r) {
-                int s = (256 * r) / tiles;
-                if (s < 1) s = 1;
-                if (s > kt_total / 4) s = kt_total / 4 > 0 ? kt_total / 4 : 1;  // >= 4 K tiles per block
-                const int blocks = tiles * s;
-                const double fill = (double)blocks / (256.0 * ((blocks + 255) / 256));
-                if (fill > best + 1e-9) { best = fill; splits = s; }
-                if (fill >= 0.93) break;
-            }
-        }
+        const int splits = plan_wgrad_splits(plan_knobs(), tiles, kt_total);   // for the round-1 / bf16-planes kernels
         const bool vec = (a->seg_n % 4 == 0) && (a->K % 4 == 0) && (a->ldy % 4 == 0) && (a->ldx % 4 == 0) &&
                          vb_aligned16(p.A) && vb_aligned16(a->X);
         p.epi = EPI_ATOMIC;
@@ -1114,14 +717,48 @@ extern "C" int vb_linear_bwd_weight(void* stream, const vb_linear_bwd_weight_arg
         const int k_main = p.K / V2_BK * V2_BK;
         if (vec2 && k_main >= 256 && k_main != p.K) {
             // contraction (row count) not a multiple of 16: aligned bulk + a tiny launch for the <= 15 leftover rows
-            GemmP m = p, t = p;
-            m.K = k_main; m.bseg = k_main;
+            GemmP m, t;
+            split_ragged_k(p, k_main, p.lda, p.ldb, m, t);
             if (int e = launch_gemm<false, false>(st, m, vec, -1, splits, 1)) return e;
-            t.K = p.K - k_main; t.bseg = t.K; t.A = p.A + (long)k_main * p.lda; t.B[0] = p.B[0] + (long)k_main * p.ldb;
             if (int e = launch_gemm<false, false>(st, t, false, -1, 1, 0)) return e;
             continue;
         }
         if (int e = launch_gemm<false, false>(st, p, vec, -1, splits, vec2 ? 1 : 0)) return e;
     }
     return 0;
+}
+
+// ---- setters of the process-wide settings ------------------------------------------------------------------------
+extern "C" int vb_set_gemm_mode(int planes) {
+    const int prev = plan_knobs().gemm_mode;
+    if (planes >= 0 && planes <= 3) plan_knobs().gemm_mode = planes;
+    return prev;
+}
+
+extern "C" int vb_set_gemm_tile(int code) {
+    const int prev = plan_knobs().tile_code;
+    if (code == -1 || code == 0 || code == 22 || code == 33 || code == 34 || code == 43 || code == 44 || code == 434 ||
+        code == 433 || code == 324 || code == 323)
+        plan_knobs().tile_code = code;
+    return prev;
+}
+
+extern "C" int vb_set_gemm_v4(int mode) {
+    const int prev = plan_knobs().v4_mode;
+    if (mode >= 0 && mode <= 2) plan_knobs().v4_mode = mode;
+    return prev;
+}
+
+// Laboratory hook (tools/gemm_lab.cpp, not part of the product ABI): device buffer of 2 x uint64 receiving
+// {shader cycles of the K loop of block 128, its K steps} of every following second-generation GEMM launch.
+extern "C" void vblab_gemm_cycles(unsigned long long* dev_buf) { g_dbg = dev_buf; }
+// Laboratory / test hook (not part of the product ABI): configuration code of the most recent forward / dgrad launch
+// that reached the planner (0 = it ran on the 4-wave blocks)
+extern "C" int vblab_last_gemm_v4_cfg(void) { return g_v4_last_cfg; }
+// Laboratory / test hook (not part of the product ABI): force one persistent-kernel configuration (plan_v4 code, 0 = the
+// planner's choice) wherever the shape allows it. Returns the previous value.
+extern "C" int vblab_set_gemm_v4_cfg(int cfg) {
+    const int prev = plan_knobs().v4_force_cfg;
+    plan_knobs().v4_force_cfg = cfg;
+    return prev;
 }

@@ -19,12 +19,14 @@
 // operands land under the epilogue); ONE barrier per K tile. A K tile = four MFMA steps (K = 16 each) on two static fragment
 // register sets: step s multiplies set s & 1 while set (s + 1) & 1 is read from LDS; the barrier sits between steps 2 and 3,
 // after the last read of the stage.
+#include "det_workspace.h"
 #include "gemm_core.h"
 #include <type_traits>
 
 namespace {
 
 using namespace vbgemm;
+using namespace vbdet;
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -383,7 +385,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::PER_CU == 1 ? 1 : 3) void gemm_b
 // persistent blocks per launch (VB_BF16_GRID, a multiple of 8, default = the 256 CUs): with fewer, two launches of
 // different streams share the chip side by side instead of one after the other
 inline int hb_grid_limit() {
-    static const int g = [] { const char* e = getenv("VB_BF16_GRID"); const int v = e ? atoi(e) : 256; return v >= 8 && v <= 256 ? v / 8 * 8 : 256; }();
+    static const int g = [] { const int v = vb_env_int("VB_BF16_GRID", 256); return v >= 8 && v <= 256 ? v / 8 * 8 : 256; }();
     return g;
 }
 
@@ -408,7 +410,7 @@ int launch_hb_cfg(hipStream_t st, HbP p) {
 // more than the overlapped epilogues win back (q|k|v forward 44.8 -> 67.7 us).
 template <int OUT, int EPI>
 int launch_hb(hipStream_t st, const HbP& p) {
-    static const int half = [] { const char* e = getenv("VB_BF16_HALF"); return e ? atoi(e) : 1; }();
+    static const int half = vb_env_int("VB_BF16_HALF", 1);
     const int tiles_full = ((p.M + 255) / 256) * p.tiles_n;
     const bool use_half = half == 2 || (half == 1 && tiles_full <= 128);
     return use_half ? launch_hb_cfg<OUT, EPI, HbHalf>(st, p) : launch_hb_cfg<OUT, EPI, HbFull>(st, p);
@@ -959,7 +961,7 @@ extern "C" int vb_linear_bf16(void* stream, const vb_linear_bf16_args* a) {
     p.drop_scale = drop ? 1.0f / (1.0f - a->dropout_p) : 1.0f;
     p.seed = a->seed;
     p.epoch = vb_seed_epoch();
-    static const int lab_flags = [] { const char* e = getenv("VB_BF16_FLAGS"); return e ? atoi(e) : 0; }();
+    static const int lab_flags = vb_env_int("VB_BF16_FLAGS", 0);
     p.flags = lab_flags;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a->C32 != nullptr) {
@@ -1002,11 +1004,11 @@ extern "C" int vb_wgrad_bf16(void* stream, const vb_wgrad_bf16_args* a) {
     // main loop costs ~1.0 us per contraction tile, its epilogue - 128 KiB of fp32 atomics that execute at the memory side,
     // ~1.7 TB/s for the whole chip - ~0.075 us per unit IN FLIGHT ANYWHERE (0.12 in the model: in the step, where other streams compete for the memory side, fewer splits measured +0.7 %); rounds of 256 units. More splits shorten the main
     // loop and lengthen the atomics: the first version's "fill two rounds" rule spent 30 - 50 % of a launch in atomics.
-    static const float t_k = [] { const char* e = getenv("VB_BF16_WG_TK"); return e ? (float)atof(e) : 1.0f; }();
-    static const float t_e = [] { const char* e = getenv("VB_BF16_WG_TE"); return e ? (float)atof(e) : 0.12f; }();
+    static const float t_k = (float)vb_env_float("VB_BF16_WG_TK", 1.0);
+    static const float t_e = (float)vb_env_float("VB_BF16_WG_TE", 0.12);
     // deterministic form: a unit's 128 KiB leave as plain 16-byte stores (t_d per unit), and the reduce pass reads every
     // partial once and updates dW: (splits + 2) x 4 N K bytes at ~3.5 TB/s + its launch
-    static const float t_d = [] { const char* e = getenv("VB_BF16_WG_TD"); return e ? (float)atof(e) : 0.04f; }();
+    static const float t_d = (float)vb_env_float("VB_BF16_WG_TD", 0.04);
     hipStream_t st = static_cast<hipStream_t>(stream);
     size_t slice_bytes = 0;
     float* slice = det_on() ? det_slice(st, &slice_bytes) : nullptr;
@@ -1035,7 +1037,7 @@ extern "C" int vb_wgrad_bf16(void* stream, const vb_wgrad_bf16_args* a) {
         p.ws = slice;
         p.ws_b = slice + (size_t)p.splits * p.tiles * 32768;
     }
-    static const int lab_flags = [] { const char* e = getenv("VB_BF16_FLAGS"); return e ? atoi(e) : 0; }();
+    static const int lab_flags = vb_env_int("VB_BF16_FLAGS", 0);
     p.flags = lab_flags;
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS);

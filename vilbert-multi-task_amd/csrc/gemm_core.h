@@ -1,5 +1,6 @@
-// Shared pieces of the GEMM kernels (gemm.hip): launch parameters, tile planning, XCD-aware block map and
-// the fused epilogues.
+// Device-side pieces shared by the fp32 GEMM kernels (gemm.hip, gemm_planes.hip, gemm_v2.hip): LDS geometry of the
+// round-1 tiles, XCD-aware block map, the fused epilogues, operand staging, and the launchers each translation unit
+// offers the others. The launch parameters (GemmP, EPI_*) and every planner live in gemm_plan.h (host-only).
 #pragma once
 #include "common.h"
 #include "rng.h"
@@ -11,41 +12,6 @@ constexpr int KC_LD = BK + 4;
 constexpr int OPER_SZ = 128 * KC_LD;         // 2560 floats >= 16 * 132 (row-contiguous big tile)
 constexpr int STAGE_SZ = 2 * OPER_SZ;        // A + B
 constexpr int GEMM_LDS_BYTES = 2 * STAGE_SZ * 4;  // 40,960 B
-
-// EPI_DGELU: c = gelu(v), D = gelu'(v) (the activation derivative saved for backward); EPI_MUL: c = v * mul
-// (the saved derivative applied to the incoming gradient in the dgrad epilogue)
-enum { EPI_GENERIC = 0, EPI_STORE, EPI_GELU, EPI_RES, EPI_PRE_GELU, EPI_ACCUM, EPI_ATOMIC, EPI_RES_DROP, EPI_DGELU,
-       EPI_MUL };
-
-struct GemmP {
-    int M, N, K;
-    const float* A; long lda;
-    const float* B[VB_MAX_SEGMENTS]; long ldb; int bseg;   // B row segments (stacked weights)
-    const float* bias[VB_MAX_SEGMENTS];
-    float* C[VB_MAX_SEGMENTS]; long ldc; int cseg;          // C row segments (wgrad of stacked weights)
-    float* colsum[VB_MAX_SEGMENTS];  // row-contiguous A only: colsum[i] += sum_k A[i][k] (bias gradient)
-    const float* R; long ldr;
-    float* P; long ldp;
-    float* D; long ldd;          // activation derivative act'(pre-activation) (may be null)
-    const float* mul; long ldmul;  // elementwise multiplier of the result (may be null)
-    int act;
-    int accumulate;       // C += result
-    int tiles_n;          // big-tile grid columns
-    int n_big, n_small;   // blocks [0, n_big): big tiles; [n_big, n_big + n_small): small tiles
-    int m_split;          // second-generation kernel: rows [0, m_split) are cut into the taller tiles
-    int ktiles_per_split; // split-K (gridDim.y > 1): atomicAdd into C
-    int epi;              // EPI_* fast path of interior tiles
-    int flags;            // tuning knobs (VB_GEMM_FLAGS): 1 = raise wave priority around the MFMA block
-    float drop_p, drop_scale;  // dropout on the activated value, before the residual (0 = off)
-    uint64_t seed;
-    const uint64_t* epoch;     // device step counter mixed into the seed (vb_set_seed_epoch), may be null
-    unsigned long long* dbg;   // lab only (vblab_gemm_cycles): block 0 stores its shader-clock span here
-    // deterministic split-K (vb_set_deterministic): split s stores its partial product to det_ws + s * det_stride as a
-    // plain [M, N] matrix (and its bias-gradient partial to det_cs + s * M) instead of adding into C with atomics; a
-    // second kernel sums the partials in split order (splitk_reduce_kernel)
-    float* det_ws; float* det_cs; long det_stride;
-    int det_cs_parts;          // bias-gradient partials per (split, row): 1, or 2 for the bf16-plane kernels (two threads per row)
-};
 
 // XCD-aware bijective remap of a linear block id over `nb` blocks (guide T1).
 __device__ __forceinline__ int xcd_swizzle(int b, int nb) {
@@ -185,23 +151,6 @@ __device__ __forceinline__ void tile_epilogue(const GemmP& p, const f32x16 (&acc
     }
 }
 
-// Tile plan: full rounds of 256 big tiles, leftover as small tiles when that shortens the tail.
-inline void plan_tiles(GemmP& p, int splits, bool planes_mode) {
-    const int tiles_m = (p.M + 127) / 128;
-    p.tiles_n = (p.N + 127) / 128;
-    const int total = tiles_m * p.tiles_n;
-    static const int hybrid = [] { const char* e = getenv("VB_GEMM_HYBRID"); return e ? atoi(e) : 1; }();
-    const int left = total % 256;
-    // 4 * left small tiles cost ceil(4 left / 256) quarter-rounds vs one full big round (= 4). A small tile
-    // runs at ~3/4 of a big tile's MFMA efficiency in the fp32 kernel (re-cut when < 4 quarter-rounds) but
-    // at ~1/2 in the bf16-planes kernel, whose per-thread split work does not shrink with the tile
-    // (re-cut only when the tail fits ONE quarter-round).
-    const int limit = planes_mode ? 2 : 4;
-    const bool recut = hybrid && splits == 1 && left > 0 && (4 * left + 255) / 256 < limit && (p.cseg % 64) == 0;
-    p.n_big = recut ? total - left : total;
-    p.n_small = recut ? 4 * left : 0;
-}
-
 // Staging of one R x 16 operand tile into registers (R / 64 float4 per thread).
 // k-contiguous operand (global [rows][ld]): thread t owns rows (t >> 2) + 64 it and the four k values
 // 4 (t & 3) .. +3 of every K tile, so the row base pointers are computed once per block (this is also
@@ -238,15 +187,9 @@ int launch_gemm_v2_tn(hipStream_t st, const GemmP& p, int tm1, int tm2, int tn, 
 // persistent one-block-per-CU kernels (gemm_v4.h): 288 x (32 tn) tiles, forward / dgrad layouts, no split-K
 int launch_gemm_v4_nt(hipStream_t st, const GemmP& p, int tn);
 int launch_gemm_v4_nn(hipStream_t st, const GemmP& p, int tn);
-// persistent weight-gradient kernel (gemm_v4w.h); the launch parameters are filled by plan_v4w (gemm.hip)
+// persistent weight-gradient kernel (gemm_v4w.h); the launch parameters are filled by plan_v4w (gemm_plan.h)
 int launch_gemm_v4_tn(hipStream_t st, const GemmP& p, int cfg);
 
-// Deterministic split-K workspace (gemm.hip, vb_set_deterministic) for the kernels of other translation units (gemm_bf16.hip):
-// det_on() = the setting; det_slice(stream, &bytes) = the slice of (current device, stream) or nullptr (no workspace / all
-// slices taken); det_fallback() counts a launch that ran with atomics although the setting is on.
-bool det_on();
-float* det_slice(hipStream_t st, size_t* slice_bytes);
-void det_fallback();
 // bf16-planes kernels (gemm_planes.hip, one object per plane count): launch for operand layouts (a_kc, b_kc)
 int launch_gemm_planes3(hipStream_t st, const GemmP& p, bool vec, int splits, bool a_kc, bool b_kc);
 int launch_gemm_planes2(hipStream_t st, const GemmP& p, bool vec, int splits, bool a_kc, bool b_kc);

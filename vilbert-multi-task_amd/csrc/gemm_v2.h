@@ -31,7 +31,6 @@
 
 namespace vbgemm {
 
-constexpr int V2_BK = 16;
 constexpr int V2_STAGES = 3;
 
 template <bool KC, int R>

@@ -621,7 +621,7 @@ extern "C" int vb_linear_fwd_mx(void* stream, const vb_linear_mx_args* a) {
     p.tiles_n = p.N / MX_BN;
     p.tiles = ((p.M + MX_BM - 1) / MX_BM) * p.tiles_n;
 #ifdef VB_GEMM_LAB
-    static const int flags = [] { const char* e = getenv("VB_MX_FLAGS"); return e ? atoi(e) : 0; }();
+    static const int flags = vb_env_int("VB_MX_FLAGS", 0);
     p.flags = flags;
 #endif
     hipStream_t st = static_cast<hipStream_t>(stream);
