@@ -10,9 +10,13 @@
 
 NVIDIA apex does not exist on ROCm images. On this package that mode is the bf16 stream: bfloat16
 activations / gradients, fp32 master weights that the native AdamW updates directly - bf16 has fp32's exponent range, so
-there is no loss scale to manage: `backward(loss)` is `loss.backward()`, `loss_scale` reads 1.0 and never overflows.
-`max_grad_norm` (FusedAdam's global-norm clipping, which apex applies through FP16_Optimizer's combined scale) is one norm
-over the flat gradient arena + one in-place scale of it (two torch calls on one buffer; declared in DESIGN.md section 1).
+there is no loss scale to manage: `backward(loss)` is `loss.backward()` and `loss_scale` reads 1.0.
+`max_grad_norm` (FusedAdam's global-norm clipping, which apex applies through FP16_Optimizer's combined scale) is native
+(vilbert.optim.AdamW, csrc/optimizer.hip): one norm pass over every gradient the step updates - arena slice or not, whoever
+owns the arena, whatever the order in which optimizer and DistributedDataParallel were built - leaves the clip coefficient
+on the device and the update kernel multiplies it in as it loads the gradients; `.grad` is not rewritten (apex passes its
+scale to the kernel the same way). As in apex, a step whose gradients hold an inf / NaN is skipped - parameters and moments
+keep their bits - and `FP16_Optimizer.overflow` reports it.
 """
 import torch
 
@@ -31,24 +35,20 @@ class FusedAdam(AdamW):
         if eps_inside_sqrt:
             raise RuntimeError("FusedAdam (MI355X-native): eps_inside_sqrt is not supported")
         super(FusedAdam, self).__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
-                                        correct_bias=bool(bias_correction))
-        self.max_grad_norm = float(max_grad_norm)
+                                        correct_bias=bool(bias_correction), max_grad_norm=max_grad_norm,
+                                        skip_nonfinite=True)
 
     def clip_(self):
-        """Global-norm clipping of every gradient this optimizer owns; returns the norm (a device scalar) or None."""
+        """In-place global-norm clipping of the `.grad` tensors of this optimizer's parameters (torch, eager); returns
+        the norm (a device scalar) or None. step() does NOT call it - it clips inside the native update without touching
+        the gradients; this stays for callers that want clipped `.grad` tensors. It goes through the parameters, not a
+        gradient arena, so it does not matter who owns the arena."""
         if self.max_grad_norm <= 0.0:
             return None
-        if self._arena is not None:
-            flat = self._arena.flat
-            norm = torch.linalg.vector_norm(flat)
-            flat.mul_(torch.clamp(self.max_grad_norm / (norm + 1e-6), max=1.0))
-            return norm
-        grads = [p.grad for g in self.param_groups for p in g["params"] if p.grad is not None]
-        return torch.nn.utils.clip_grad_norm_([p for g in self.param_groups for p in g["params"] if p.grad is not None],
-                                              self.max_grad_norm) if grads else None
+        params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        return torch.nn.utils.clip_grad_norm_(params, self.max_grad_norm) if params else None
 
     def step(self, closure=None, **_apex_kwargs):      # (apex passes grads / output_params / scale / grad_norms)
-        self.clip_()
         return super(FusedAdam, self).step(closure)
 
 
@@ -66,8 +66,14 @@ class FP16_Optimizer(torch.optim.Optimizer):
         self.state = init_optimizer.state
         self.dynamic_loss_scale = bool(dynamic_loss_scale)
         self.static_loss_scale = static_loss_scale
-        self.overflow = False
         self.cur_scale = 1.0
+
+    @property
+    def overflow(self):
+        """Whether the last step was skipped because of non-finite gradients. Read lazily from the device flag the norm
+        kernel wrote: step() itself never synchronises, reading this does."""
+        skipped = getattr(self.optimizer, "last_step_skipped", None)
+        return bool(skipped()) if skipped is not None else False
 
     @property
     def loss_scale(self):

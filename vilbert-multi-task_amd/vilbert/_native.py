@@ -340,6 +340,17 @@ SIGNATURES = {
     "vb_layer_bwd": (ctypes.c_int, [_P, ctypes.POINTER(LayerArgs)]),
 }
 
+# include/vilbert_hip_ext.h (entry points added after the ABI-18 export list was frozen; prefix vbx_), mirrored one to one
+# (checked by tests/test_optim_clip.py against the header text)
+EXT_SIGNATURES = {
+    "vbx_grad_norm_workspace": (_I64, [_I32]),
+    "vbx_grad_norm": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I32, _F32, _F32, _I32, _P, _P]),
+    "vbx_adamw_step_scaled": (ctypes.c_int, [_P, _I32, _P, _P, _P, _I32, _P, _I32]),
+}
+# layout of the device state vbx_grad_norm writes (VB_GRAD_STATE_* of the header)
+GRAD_STATE_FLOATS = 8
+GRAD_STATE_SUMSQ, GRAD_STATE_NORM, GRAD_STATE_COEF, GRAD_STATE_FINITE, GRAD_STATE_SKIPPED = 0, 1, 2, 3, 4
+
 _lib = None
 
 
@@ -352,7 +363,7 @@ def lib():
                 "libvilbert_hip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C vilbert-multi-task_amd/csrc`). There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

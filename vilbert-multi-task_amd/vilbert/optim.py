@@ -21,9 +21,22 @@ CHUNK_ELEMS = 64 * 1024
 class AdamW(Optimizer):
     """Adam with decoupled weight decay; ``correct_bias=False`` reproduces the original BERT optimizer
     (train_tasks.py:426). State layout (``step``, ``exp_avg``, ``exp_avg_sq``) matches pytorch-transformers, so
-    the ``.tar`` checkpoints the reference scripts write stay interchangeable."""
+    the ``.tar`` checkpoints the reference scripts write stay interchangeable.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    ``max_grad_norm`` > 0 clips the global norm of all gradients of the step (the coefficient of
+    ``torch.nn.utils.clip_grad_norm_``), ``grad_scale`` multiplies every gradient (e.g. 1 / world size behind a SUM
+    exchange; the norm is that of the scaled gradients), ``skip_nonfinite`` leaves parameters and moments untouched when a
+    gradient is inf / NaN (or the fp32 sum of squares overflows). All three are native (csrc/optimizer.hip): one norm pass
+    over the gradients, a device-resident coefficient the update kernel multiplies in as it loads them - no host
+    synchronisation, capturable by GraphedTrainStep. Unlike ``clip_grad_norm_`` the ``.grad`` tensors are NOT modified
+    (apex's FusedAdam passes its scale the same way). The norm covers exactly the tensors the step updates, whether their
+    gradient is a slice of the gradient arena or a tensor of its own. ``state["step"]`` advances on the host also for a
+    skipped step (the skip is decided on the device); that only matters with ``correct_bias=True``, which neither
+    reference script uses. With the defaults step() is the plain launch: no norm pass, no extra buffers. The three values
+    are plain attributes; a captured step keeps the values it was captured with."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
+                 max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
         if lr < 0.0:
             raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
         if not 0.0 <= betas[0] < 1.0:
@@ -32,6 +45,12 @@ class AdamW(Optimizer):
             raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
         if not 0.0 <= eps:
             raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        if not (0.0 <= float(max_grad_norm) < math.inf):
+            raise ValueError("Invalid max_grad_norm: {} - should be finite and >= 0.0 (0 = no clipping)".format(max_grad_norm))
+        if not math.isfinite(float(grad_scale)):
+            raise ValueError("Invalid grad_scale: {} - should be finite".format(grad_scale))
+        self.max_grad_norm, self.grad_scale, self.skip_nonfinite = float(max_grad_norm), float(grad_scale), bool(skip_nonfinite)
+        self._grad_state = None          # device floats written by vbx_grad_norm (_native.GRAD_STATE_*), one per optimizer
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
         super(AdamW, self).__init__(params, defaults)
         self._plan_key, self._plan = None, None
@@ -128,12 +147,63 @@ class AdamW(Optimizer):
             ev = torch.cuda.Event()
             ev.record()
             plan["events"][k] = ev
-        N.check(N.lib().vb_adamw_step(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
-                                      plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS),
-                "vb_adamw_step")
+        if self._scaled():
+            partials, state = self._clip_buffers(plan, device, capturing)
+            skip = int(self.skip_nonfinite)
+            N.check(N.lib().vbx_grad_norm(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
+                                          plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
+                                          self.max_grad_norm, self.grad_scale, skip, partials.data_ptr(), state.data_ptr()),
+                    "vbx_grad_norm")
+            N.check(N.lib().vbx_adamw_step_scaled(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
+                                                  plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
+                                                  state.data_ptr(), skip), "vbx_adamw_step_scaled")
+        else:
+            N.check(N.lib().vb_adamw_step(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
+                                          plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS),
+                    "vb_adamw_step")
         N.weights_changed()
         del keep
         return loss
+
+    def _scaled(self):
+        return self.max_grad_norm > 0.0 or self.grad_scale != 1.0 or self.skip_nonfinite
+
+    def _clip_buffers(self, plan, device, capturing):
+        """Fixed-address buffers of the norm pass: the per-chunk partial sums belong to the plan, the state (norm,
+        coefficient, finite flag, skipped-step count) to the optimizer - the count survives a change of plan."""
+        if self._grad_state is None or "partials" not in plan:
+            if capturing:
+                raise RuntimeError("AdamW: the first clipped / scaled step of a plan allocates its buffers and must run "
+                                   "eagerly before a graph capture (GraphedTrainStep's warm-up does)")
+            if self._grad_state is None:
+                self._grad_state = torch.zeros(N.GRAD_STATE_FLOATS, dtype=torch.float32, device=device)
+            plan["partials"] = torch.empty(int(N.lib().vbx_grad_norm_workspace(plan["n_chunks"])), dtype=torch.float32,
+                                           device=device)
+        return plan["partials"], self._grad_state
+
+    def _need_state(self):
+        if self._grad_state is None:
+            raise RuntimeError("AdamW: no clipped / scaled step has run yet (max_grad_norm, grad_scale and skip_nonfinite "
+                               "are all at their defaults, or step() was never called)")
+        return self._grad_state
+
+    @property
+    def grad_norm(self):
+        """Global norm of the (scaled) gradients of the last clipped / scaled step: a 0-dim DEVICE tensor that views the
+        state the norm kernel writes - reading the property does not synchronise, and the same tensor shows the value of
+        every later step (also of graph replays). Clone it to keep a value."""
+        return self._need_state()[N.GRAD_STATE_NORM]
+
+    def skipped_steps(self):
+        """Number of steps skipped because of non-finite gradients (skip_nonfinite=True). Reads the device counter:
+        SYNCHRONISES with the device."""
+        return 0 if self._grad_state is None else int(self._grad_state[N.GRAD_STATE_SKIPPED].item())
+
+    def last_step_skipped(self):
+        """Whether the last step was skipped (skip_nonfinite=True and non-finite gradients). SYNCHRONISES with the device."""
+        if not self.skip_nonfinite or self._grad_state is None:
+            return False
+        return float(self._grad_state[N.GRAD_STATE_FINITE].item()) == 0.0
 
     def _fill_table(self, plan, entries, pointers=True):
         """Per-step columns of the launch table: gradient pointers and the hyper-parameters of this step (vectorised:
