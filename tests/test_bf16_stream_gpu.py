@@ -27,13 +27,7 @@ def _rand(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=torch.Generator().manual_seed(seed)) * scale
 
 
-def _close16(got, want64, mag64, what):
-    """got (bf16 or fp32 tensor) vs float64 `want`: fp32 accumulation + one bf16 rounding (fp32 outputs: accumulation only)."""
-    g = got.detach().cpu().double()
-    assert g.shape == want64.shape and torch.isfinite(g).all(), what
-    tol = 3e-6 * mag64 + 1e-5 + (want64.abs() / 256 if got.dtype == BF16 else 0.0)
-    err = (g - want64).abs()
-    assert (err <= tol).all(), "%s: worst err / tol %.3f" % (what, float((err / tol).max()))
+_close16 = helpers.close16     # fp32 accumulation + one bf16 rounding, against float64 on the same bf16 values
 
 
 @pytest.mark.parametrize("M,nseg,seg_n,K", [(300, 1, 768, 768), (77, 3, 256, 128), (640, 1, 1024, 2048), (1, 1, 256, 128),
@@ -126,14 +120,10 @@ def test_layernorm16_forward_backward(rows, cols):
     dy = _rand(rows, cols, seed=rows + 1).to(BF16)
     g, b = 1 + 0.1 * _rand(cols, seed=3), 0.1 * _rand(cols, seed=4)
     y, mean, rstd = ops16.layernorm_fwd(x.to(DEV), g.to(DEV), b.to(DEV), 1e-12, want_stats=True)
-    xd = x.double()
-    mu = xd.mean(1, keepdim=True)
-    var = ((xd - mu) ** 2).mean(1, keepdim=True)
-    xh = (xd - mu) / torch.sqrt(var + 1e-12)
-    _close16(y, g.double() * xh + b.double(), torch.ones(rows, cols, dtype=torch.float64) * 4, "LayerNorm forward")
-    assert (mean.cpu().double() - mu[:, 0]).abs().max() < 1e-5 and (rstd.cpu().double() * torch.sqrt(var[:, 0] + 1e-12) - 1).abs().max() < 1e-5
-    gd = dy.double() * g.double()
-    want = (gd - gd.mean(1, keepdim=True) - xh * (gd * xh).mean(1, keepdim=True)) / torch.sqrt(var + 1e-12)
+    ref = helpers.layernorm16_reference(x, dy, g, b, 1e-12)
+    xh, want = ref["xh"], ref["dx"]
+    _close16(y, ref["y"], torch.ones(rows, cols, dtype=torch.float64) * 4, "LayerNorm forward")
+    assert (mean.cpu().double() - ref["mean"]).abs().max() < 1e-5 and (rstd.cpu().double() * torch.sqrt(ref["var"] + 1e-12) - 1).abs().max() < 1e-5
     seed, p = 1234567, 0.1
     dx, dgam, dbet, dxd = ops16.layernorm_bwd(dy.to(DEV), x.to(DEV), mean, rstd, g.to(DEV), drop=(p, seed))
     scale = torch.ones(rows, cols, dtype=torch.float64) * float(want.abs().max()) * 4

@@ -44,22 +44,18 @@ __device__ __forceinline__ f32x4 ld4(const io_t* p) {
                  __uint_as_float(w.y & 0xffff0000u)};
 }
 __device__ __forceinline__ float ld1(const io_t* p) { return __uint_as_float((unsigned)*p << 16); }
-__device__ __forceinline__ void st1(io_t* p, float v) {
-    const unsigned u = __float_as_uint(v);
-    *p = (io_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+__device__ __forceinline__ void st1(io_t* p, float v) { *p = (io_t)vb_bf16_round(v); }
 // one output row piece: element a[dt][r] belongs to column 16 dt + c of the row; `op` already points at column c. Lanes c and
 // c ^ 1 trade one value per pair of 16-column blocks, so that every lane stores TWO adjacent bf16 columns (4 bytes) per pair
 // instead of one 2-byte element per block: half the store instructions (these kernels' tails are store-issue-bound).
 template <int DS>
 __device__ __forceinline__ void store_cols(io_t* op, int c, const f32x4 (&a)[DS], int r) {
-    auto bf = [](float v) -> unsigned { const unsigned u = __float_as_uint(v); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
 #pragma unroll
     for (int k = 0; k < DS / 2; ++k) {
         const float even = a[2 * k][r], odd = a[2 * k + 1][r];
         const float recv = __shfl_xor((c & 1) ? even : odd, 1, 64);
-        if (c & 1) *reinterpret_cast<unsigned*>(op + 32 * k + 15) = bf(recv) | (bf(odd) << 16);     // columns 32 k + 16 + c - 1, + c
-        else *reinterpret_cast<unsigned*>(op + 32 * k) = bf(even) | (bf(recv) << 16);               // columns 32 k + c, + c + 1
+        if (c & 1) *reinterpret_cast<unsigned*>(op + 32 * k + 15) = vb_bf16_pack(recv, odd);    // columns 32 k + 16 + c - 1, + c
+        else *reinterpret_cast<unsigned*>(op + 32 * k) = vb_bf16_pack(even, recv);             // columns 32 k + c, + c + 1
     }
 }
 #else

@@ -40,10 +40,7 @@ struct AttnMxP {
     int v_rows;                          // V rows each wave stages in LDS (= n_k: tile rows past it are read as row n_k - 1)
 };
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+__device__ __forceinline__ unsigned short bf16_bits(float v) { return (unsigned short)vb_bf16_round(v); }
 
 constexpr int AMX_ROWS = 48;           // longest query / key sequence (three 16-row tiles)
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bf16_round.h"  // host-only part: the one fp32 -> bf16 rounding (NaN-safe) of every bf16 store
 #include "gemm_plan.h"   // host-only part: the C ABI header, vb_aligned16, vb_env_int / vb_env_float
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -59,11 +59,8 @@ struct HbCfg {
 using HbFull = HbCfg<256, 3, 2>;
 using HbHalf = HbCfg<128, 2, 1>;
 
-__device__ __forceinline__ unsigned short bf16_rne(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return (unsigned)bf16_rne(lo) | ((unsigned)bf16_rne(hi) << 16); }
+__device__ __forceinline__ unsigned short bf16_rne(float v) { return (unsigned short)vb_bf16_round(v); }
+__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return vb_bf16_pack(lo, hi); }
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 

@@ -229,10 +229,7 @@ __device__ __forceinline__ void mx_loader(const MxP& p, const unsigned lds0, con
     }
 }
 
-__device__ __forceinline__ unsigned short bf16_rne(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+__device__ __forceinline__ unsigned short bf16_rne(float v) { return (unsigned short)vb_bf16_round(v); }
 
 // KIND: what the launch writes = how the MFMA product is oriented = who owns what in the epilogue.
 //   MX_OUT_F32 / MX_OUT_BF16: natural product (accumulator rows = output rows in registers, lane & 31 = output column) on a

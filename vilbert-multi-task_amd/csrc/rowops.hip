@@ -388,7 +388,6 @@ __global__ __launch_bounds__(256) void layernorm16_mx_kernel(long rows, int n_co
     wave_sum_n(var);
     opaque();
     const int nkt = n_cols >> 7;
-    auto bf = [](float f) -> unsigned { const unsigned u = __float_as_uint(f); return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16; };
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int col = (i * 64 + lane) * 4;
@@ -407,7 +406,7 @@ __global__ __launch_bounds__(256) void layernorm16_mx_kernel(long rows, int n_co
             if (ok) v = g * ((v - mean[r]) * rstd) + b;
             if (live)
                 *reinterpret_cast<uint2*>(y + rrow[r] * n_cols + col) =
-                    uint2{bf(v[0]) | (bf(v[1]) << 16), bf(v[2]) | (bf(v[3]) << 16)};
+                    uint2{vb_bf16_pack(v[0], v[1]), vb_bf16_pack(v[2], v[3])};
             // (the cross-lane steps inside run for every lane; the stores of the rows that do not exist are masked)
             mx_quant_chunk(v, live, lane, have[r] ? kt : nkt, nkt, reinterpret_cast<unsigned*>(q + rrow[r] * ldq + (ok ? col : 0)),
                            mxs + (long)(kt < nkt ? kt : 0) * mxs_rows + rrow[r]);

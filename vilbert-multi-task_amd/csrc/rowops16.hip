@@ -8,10 +8,7 @@
 
 namespace {
 
-__device__ __forceinline__ unsigned short bf16_rne(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-}
+__device__ __forceinline__ unsigned short bf16_rne(float v) { return (unsigned short)vb_bf16_round(v); }
 __device__ __forceinline__ f32x4 load4(const unsigned short* p) {
     const uint2 w = *reinterpret_cast<const uint2*>(p);
     return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
@@ -22,8 +19,7 @@ __device__ __forceinline__ f32x4 unpack4(const uint2 w) {
                  __uint_as_float(w.y & 0xffff0000u)};
 }
 __device__ __forceinline__ void store4(unsigned short* p, const f32x4 v) {
-    *reinterpret_cast<uint2*>(p) = uint2{(unsigned)bf16_rne(v[0]) | ((unsigned)bf16_rne(v[1]) << 16),
-                                         (unsigned)bf16_rne(v[2]) | ((unsigned)bf16_rne(v[3]) << 16)};
+    *reinterpret_cast<uint2*>(p) = uint2{vb_bf16_pack(v[0], v[1]), vb_bf16_pack(v[2], v[3])};
 }
 
 template <int R>
