@@ -573,7 +573,7 @@ typedef struct {
 int vb_concap_finish_batch(void* stream, const vb_concap_batch* a);
 
 /* ------------------------------------------------------------------------------------------
- * bf16 TRAINING path (round 5; csrc/gemm_bf16.hip, rowops16.hip, attention.hip). Replaces the reference's reduced-precision
+ * bf16 TRAINING path (round 5; csrc/gemm_bf16.hip, layernorm.hip, attention.hip). Replaces the reference's reduced-precision
  * training mode - `model.half()` + apex FP16_Optimizer, /root/reference/train_concap.py:443-461,504-505 (train_tasks.py has
  * the same block) - the way gfx950 wants it: bf16 activations / saved tensors / activation gradients in HBM (no loss scaling:
  * bf16 has fp32's exponent range), v_mfma_f32_32x32x16_bf16 products with fp32 accumulation, fp32 LayerNorm statistics and

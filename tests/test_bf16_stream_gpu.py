@@ -1,4 +1,4 @@
-"""The bf16 TRAINING path (round 5; csrc/gemm_bf16.hip, rowops16.hip, attention.hip -DVB_ATTN_BF16; vilbert/ops16.py):
+"""The bf16 TRAINING path (round 5; csrc/gemm_bf16.hip, layernorm.hip, attention.hip -DVB_ATTN_BF16; vilbert/ops16.py):
 bfloat16 activations / saved tensors / activation gradients, fp32 master weights, fp32 gradient accumulation - the mode
 that replaces the reference's `model.half()` + apex FP16_Optimizer (/root/reference/train_concap.py:443-461,504-505).
 

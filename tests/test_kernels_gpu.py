@@ -212,7 +212,7 @@ def _ln64(x, g, b, eps=1e-12):
     return g * ((x - u) / torch.sqrt(s + eps)) + b
 
 
-@pytest.mark.parametrize("cols", [64, 96, 768, 1024, 2048, 4096])
+@pytest.mark.parametrize("cols", [64, 96, 768, 1024, 2048, 4096, 5000, 8192])
 def test_layernorm(ops, cols):
     x, x2 = _rand(37, cols, seed=1, scale=3.0) + 0.7, _rand(37, cols, seed=2)
     g, b = 1 + 0.1 * _rand(cols, seed=3), 0.1 * _rand(cols, seed=4)

@@ -1,5 +1,5 @@
 // Device helpers of the MX (OCP microscaling) e4m3 format shared by the kernels that emit it (mx8.hip: quantiser and
-// GEMM epilogue; rowops.hip: LayerNorm). Format and layout: see the head of mx8.hip / include/vilbert_hip.h.
+// GEMM epilogue; layernorm.hip: LayerNorm). Format and layout: see the head of mx8.hip / include/vilbert_hip.h.
 #pragma once
 #include "common.h"
 

@@ -1,4 +1,4 @@
-"""Tensor-level launchers of the bf16 TRAINING path (csrc/gemm_bf16.hip, rowops16.hip; include/vilbert_hip.h "bf16 TRAINING
+"""Tensor-level launchers of the bf16 TRAINING path (csrc/gemm_bf16.hip, layernorm.hip; include/vilbert_hip.h "bf16 TRAINING
 path"): the reduced-precision mode that replaces the reference's `model.half()` + apex FP16_Optimizer
 (/root/reference/train_concap.py:443-461,504-505). Activations, saved tensors and activation gradients are torch.bfloat16
 tensors; parameters, their gradients (the arena), LayerNorm statistics and the optimizer stay fp32. No torch arithmetic.
