@@ -13,10 +13,15 @@
 //   adamw_kernel<true>       the update with every gradient multiplied by coef on load; no store at all when the step is skipped
 // No atomics and a fixed summation order everywhere: the same gradients give the same bits. The coefficient never visits the
 // host, so the three launches are graph-capturable. The gradients themselves are only read.
+//
+// Multi-tensor RAdam step (vilbert_hip_optim.h; the reference's vilbert/optimization.py:55-98, `--optim RAdam` of train_tasks.py):
+//   radam_kernel             the same chunk walk over the same tables; the per-tensor hyper-parameters - step size, rectified
+//                            flag, lr * wd - come from a table of their own the host computes in double, the optional state of
+//                            grad_norm_finish_kernel scales the gradients and skips an overflowed step as in adamw_kernel<true>
 #include <cmath>
 
 #include "common.h"
-#include "../../include/vilbert_hip_ext.h"
+#include "../../include/vilbert_hip_optim.h"
 
 namespace {
 
@@ -69,6 +74,63 @@ __global__ __launch_bounds__(256) void adamw_kernel(const vb_adamw_tensor* __res
         const float mm = m[e] * b1 + c1 * gg, vv = v[e] * b2 + c2 * gg * gg;
         float pp = p[e] - t.step_size * (mm / (sqrtf(vv) + t.eps));
         if (t.decay > 0.f) pp -= t.decay * pp;
+        p[e] = pp; m[e] = mm; v[e] = vv;
+    }
+}
+
+// One element of the RAdam step, in the reference's order: second moment, first moment, decay on the OLD value, then the
+// adaptive step (rectified) or the momentum step. `g` arrives already scaled.
+__device__ __forceinline__ void radam_element(const vbo_radam_scalars& h, float g, float& p, float& m, float& v) {
+    v = v * h.beta2 + h.one_minus_beta2 * g * g;
+    m = m * h.beta1 + h.one_minus_beta1 * g;
+    if (h.decay != 0.f) p -= h.decay * p;
+    if (h.rectified) p -= h.step_size * (m / (sqrtf(v) + h.eps));
+    else p -= h.step_size * m;
+}
+
+// `state` == nullptr is the plain step; otherwise the coefficient and the finite flag are read once per block (uniform
+// branches) and a block of a skipped step returns before any store. coef = 1 multiplies exactly, so one kernel serves both.
+__global__ __launch_bounds__(256) void radam_kernel(const vb_adamw_tensor* __restrict__ tab,
+                                                    const vbo_radam_scalars* __restrict__ scalars,
+                                                    const int32_t* __restrict__ chunk_tensor,
+                                                    const int64_t* __restrict__ chunk_off, int chunk_elems,
+                                                    const float* __restrict__ state, int skip) {
+    float coef = 1.0f;
+    if (state != nullptr) {
+        if (skip && state[VB_GRAD_STATE_FINITE] == 0.f) return;
+        coef = state[VB_GRAD_STATE_COEF];
+    }
+    const int ti = chunk_tensor[blockIdx.x];
+    const vb_adamw_tensor t = tab[ti];
+    const vbo_radam_scalars h = scalars[ti];
+    const long off = chunk_off[blockIdx.x];
+    const long end = min((long)t.numel, off + chunk_elems);
+    float* __restrict__ p = t.param;
+    const float* __restrict__ g = t.grad;
+    float* __restrict__ m = t.exp_avg;
+    float* __restrict__ v = t.exp_avg_sq;
+    // as adamw_kernel: 16-byte accesses only where all four base pointers allow them (chunk offsets are multiples of 4)
+    const bool vec_ok = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                          reinterpret_cast<uintptr_t>(v)) & 15u) == 0;
+    const long n4 = vec_ok ? (end - off) >> 2 : 0;
+    for (long i = threadIdx.x; i < n4; i += 256) {
+        const long e = off + 4 * i;
+        f32x4 pp = *reinterpret_cast<f32x4*>(p + e);
+        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e) * coef;
+        f32x4 mm = *reinterpret_cast<f32x4*>(m + e), vv = *reinterpret_cast<f32x4*>(v + e);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float pk = pp[k], mk = mm[k], vk = vv[k];
+            radam_element(h, gg[k], pk, mk, vk);
+            pp[k] = pk; mm[k] = mk; vv[k] = vk;
+        }
+        *reinterpret_cast<f32x4*>(p + e) = pp;
+        *reinterpret_cast<f32x4*>(m + e) = mm;
+        *reinterpret_cast<f32x4*>(v + e) = vv;
+    }
+    for (long e = off + 4 * n4 + threadIdx.x; e < end; e += 256) {
+        float pp = p[e], mm = m[e], vv = v[e];
+        radam_element(h, g[e] * coef, pp, mm, vv);
         p[e] = pp; m[e] = mm; v[e] = vv;
     }
 }
@@ -173,6 +235,18 @@ extern "C" int vbx_adamw_step_scaled(void* stream, int32_t n_chunks, const vb_ad
         return VB_E_BADARG;
     if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
     hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table,
+                       chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite != 0 ? 1 : 0);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int vbo_radam_step(void* stream, int32_t n_chunks, const vb_adamw_tensor* table, const vbo_radam_scalars* scalars,
+                              const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems, const float* state,
+                              int32_t skip_nonfinite) {
+    if (table == nullptr || scalars == nullptr || chunk_tensor == nullptr || chunk_off == nullptr || n_chunks <= 0)
+        return VB_E_BADARG;
+    if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
+    hipLaunchKernelGGL(radam_kernel, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table, scalars,
                        chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite != 0 ? 1 : 0);
     VB_LAUNCH_CHECK();
     return 0;

@@ -265,6 +265,15 @@ class AdamWTensor(ctypes.Structure):
     ]
 
 
+class RAdamScalars(ctypes.Structure):
+    """vbo_radam_scalars (32 bytes; include/vilbert_hip_optim.h)"""
+    _fields_ = [
+        ("step_size", ctypes.c_float), ("decay", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+        ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("eps", ctypes.c_float),
+        ("rectified", ctypes.c_int32),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -351,6 +360,11 @@ EXT_SIGNATURES = {
 GRAD_STATE_FLOATS = 8
 GRAD_STATE_SUMSQ, GRAD_STATE_NORM, GRAD_STATE_COEF, GRAD_STATE_FINITE, GRAD_STATE_SKIPPED = 0, 1, 2, 3, 4
 
+# include/vilbert_hip_optim.h (optimizers beyond AdamW; prefix vbo_), mirrored one to one (checked by tests/test_radam.py)
+OPT_SIGNATURES = {
+    "vbo_radam_step": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32]),
+}
+
 _lib = None
 
 
@@ -363,7 +377,7 @@ def lib():
                 "libvilbert_hip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C vilbert-multi-task_amd/csrc`). There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

@@ -4,6 +4,10 @@ multi-tensor launch (csrc/optimizer.hip) instead of ~6 torch kernels per paramet
 
 Also importable as ``pytorch_transformers.optimization`` (shim package next to this one) so that the
 unchanged reference scripts pick it up.
+
+RAdam / PlainRAdam (the reference's own ``vilbert/optimization.py``, ``train_tasks.py --optim RAdam``) run on the same
+plumbing with a kernel of their own (``vbo_radam_step``); ``import vilbert.optimization`` hands them out under the
+reference's import path (vilbert/__init__.py: _OptimizationFinder).
 """
 import ctypes
 import math
@@ -17,11 +21,29 @@ from . import _native as N
 
 CHUNK_ELEMS = 64 * 1024
 
+_TABLE_DTYPE = np.dtype([
+    ("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("numel", "<i8"),
+    ("step_size", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"), ("decay", "<f4"),
+    ("reserved", "<f4")])
+_RADAM_DTYPE = np.dtype([
+    ("step_size", "<f4"), ("decay", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta1", "<f4"),
+    ("one_minus_beta2", "<f4"), ("eps", "<f4"), ("rectified", "<i4")])
 
-class AdamW(Optimizer):
-    """Adam with decoupled weight decay; ``correct_bias=False`` reproduces the original BERT optimizer
-    (train_tasks.py:426). State layout (``step``, ``exp_avg``, ``exp_avg_sq``) matches pytorch-transformers, so
-    the ``.tar`` checkpoints the reference scripts write stay interchangeable.
+
+def _check_clip_args(max_grad_norm, grad_scale):
+    if not (0.0 <= float(max_grad_norm) < math.inf):
+        raise ValueError("Invalid max_grad_norm: {} - should be finite and >= 0.0 (0 = no clipping)".format(max_grad_norm))
+    if not math.isfinite(float(grad_scale)):
+        raise ValueError("Invalid grad_scale: {} - should be finite".format(grad_scale))
+
+
+class _MultiTensorOptimizer(Optimizer):
+    """What the native optimizers share: the gradient arena, the launch tables (one vb_adamw_tensor row per tensor, chunk
+    lists on the device, uploaded through pinned memory without a host synchronisation), the fused global-norm clipping /
+    gradient scale / overflow skip (vbx_grad_norm leaves a device-resident state the update kernel reads), graph capture
+    and replay, and the weights epoch. A subclass supplies its hyper-parameters (`_fill_hyper`) and its launch (`_launch`)
+    and may append a second per-tensor table to the upload (`_EXTRA_DTYPE`: its rows follow the vb_adamw_tensor rows in
+    the same device buffer, `_extra_ptr(plan)` is their address).
 
     ``max_grad_norm`` > 0 clips the global norm of all gradients of the step (the coefficient of
     ``torch.nn.utils.clip_grad_norm_``), ``grad_scale`` multiplies every gradient (e.g. 1 / world size behind a SUM
@@ -31,31 +53,39 @@ class AdamW(Optimizer):
     synchronisation, capturable by GraphedTrainStep. Unlike ``clip_grad_norm_`` the ``.grad`` tensors are NOT modified
     (apex's FusedAdam passes its scale the same way). The norm covers exactly the tensors the step updates, whether their
     gradient is a slice of the gradient arena or a tensor of its own. ``state["step"]`` advances on the host also for a
-    skipped step (the skip is decided on the device); that only matters with ``correct_bias=True``, which neither
-    reference script uses. With the defaults step() is the plain launch: no norm pass, no extra buffers. The three values
-    are plain attributes; a captured step keeps the values it was captured with."""
+    skipped step (the skip is decided on the device). With the defaults step() is the plain launch: no norm pass, no extra
+    buffers. The three values are plain attributes; a captured step keeps the values it was captured with."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
-                 max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
-        if lr < 0.0:
-            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
-        if not 0.0 <= eps:
-            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
-        if not (0.0 <= float(max_grad_norm) < math.inf):
-            raise ValueError("Invalid max_grad_norm: {} - should be finite and >= 0.0 (0 = no clipping)".format(max_grad_norm))
-        if not math.isfinite(float(grad_scale)):
-            raise ValueError("Invalid grad_scale: {} - should be finite".format(grad_scale))
+    _NAME = "optimizer"
+    _EXTRA_DTYPE = None
+
+    def _init_native(self, max_grad_norm, grad_scale, skip_nonfinite):
+        """Before Optimizer.__init__: the three clipping attributes."""
+        _check_clip_args(max_grad_norm, grad_scale)
         self.max_grad_norm, self.grad_scale, self.skip_nonfinite = float(max_grad_norm), float(grad_scale), bool(skip_nonfinite)
         self._grad_state = None          # device floats written by vbx_grad_norm (_native.GRAD_STATE_*), one per optimizer
-        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
-        super(AdamW, self).__init__(params, defaults)
+
+    def _init_plan(self):
+        """After Optimizer.__init__ (the parameter groups exist)."""
         self._plan_key, self._plan = None, None
         self._arena = None
         self._ensure_arena()
+
+    def __setstate__(self, state):
+        """Unpickling (torch.optim.Optimizer pickles defaults, state and groups only): the clipping attributes come back
+        at their defaults, the launch plan is rebuilt at the next step."""
+        super(_MultiTensorOptimizer, self).__setstate__(state)
+        if not hasattr(self, "_grad_state"):
+            self._init_native(0.0, 1.0, False)
+            self._init_plan()
+
+    def _fill_hyper(self, plan, entries):
+        """Per-step hyper-parameter columns of the table(s), from the groups and each tensor's own step count."""
+        raise NotImplementedError
+
+    def _launch(self, plan, state, skip):
+        """Enqueue the update on the current stream; `state` is the device state of the norm pass, None = the plain step."""
+        raise NotImplementedError
 
     def _ensure_arena(self):
         """Gives the optimizer's parameters a gradient arena (arena.py: gradients at fixed addresses in one flat
@@ -75,10 +105,7 @@ class AdamW(Optimizer):
     def _build_plan(self, entries, device):
         """Static part of the launch tables for this set of tensors: chunk lists on the device and a
         host-side structured array whose grad / hyper-parameter columns are refreshed every step."""
-        tab = np.zeros(len(entries), dtype=np.dtype([
-            ("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("numel", "<i8"),
-            ("step_size", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"), ("decay", "<f4"),
-            ("reserved", "<f4")]))
+        tab = np.zeros(len(entries), dtype=_TABLE_DTYPE)
         assert tab.dtype.itemsize == ctypes.sizeof(N.AdamWTensor)
         chunk_t, chunk_o = [], []
         for i, (p, st, _g) in enumerate(entries):
@@ -88,13 +115,26 @@ class AdamW(Optimizer):
             for off in range(0, p.numel(), CHUNK_ELEMS):
                 chunk_t.append(i)
                 chunk_o.append(off)
-        # two pinned staging copies of the table (the host may run one step ahead of the device) + events
-        nbytes = tab.nbytes
+        extra = None if self._EXTRA_DTYPE is None else np.zeros(len(entries), dtype=self._EXTRA_DTYPE)
+        # two pinned staging copies of the table(s) (the host may run one step ahead of the device) + events
+        nbytes = tab.nbytes + (0 if extra is None else extra.nbytes)
         pinned = [torch.empty(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
-        return dict(tab=tab, n_chunks=len(chunk_t), pinned=pinned, events=[None, None], turn=0,
+        return dict(tab=tab, extra=extra, n_chunks=len(chunk_t), pinned=pinned, events=[None, None], turn=0,
                     dev_tab=torch.empty(nbytes, dtype=torch.uint8, device=device),
                     chunk_tensor=torch.tensor(chunk_t, dtype=torch.int32, device=device),
                     chunk_off=torch.tensor(chunk_o, dtype=torch.int64, device=device))
+
+    @staticmethod
+    def _stage(plan, k):
+        """Host tables -> pinned staging copy k."""
+        dst, tab, extra = plan["pinned"][k].numpy(), plan["tab"], plan["extra"]
+        dst[:tab.nbytes] = tab.view(np.uint8).reshape(-1)
+        if extra is not None:
+            dst[tab.nbytes:] = extra.view(np.uint8).reshape(-1)
+
+    @staticmethod
+    def _extra_ptr(plan):
+        return plan["dev_tab"].data_ptr() + plan["tab"].nbytes          # (64-byte rows in front: 16-byte aligned)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -108,11 +148,11 @@ class AdamW(Optimizer):
                 if p.grad is None:
                     continue
                 if p.grad.is_sparse:
-                    raise RuntimeError("Adam does not support sparse gradients, please consider SparseAdam instead")
+                    raise RuntimeError(self._SPARSE_MESSAGE)
                 if not p.is_cuda:
-                    raise RuntimeError("vilbert.optim.AdamW runs on HIP devices only - no CPU fallback")
+                    raise RuntimeError("vilbert.optim.%s runs on HIP devices only - no CPU fallback" % self._NAME)
                 if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("vilbert.optim.AdamW needs contiguous fp32 parameters")
+                    raise RuntimeError("vilbert.optim.%s needs contiguous fp32 parameters" % self._NAME)
                 state = self.state[p]
                 if len(state) == 0:
                     state["step"] = 0
@@ -140,7 +180,7 @@ class AdamW(Optimizer):
             plan["turn"] = k ^ 1
             if plan["events"][k] is not None:
                 plan["events"][k].synchronize()
-        plan["pinned"][k].numpy()[:] = plan["tab"].view(np.uint8).reshape(-1)
+        self._stage(plan, k)
         dev_tab = plan["dev_tab"]
         dev_tab.copy_(plan["pinned"][k], non_blocking=True)
         if not capturing:
@@ -154,13 +194,9 @@ class AdamW(Optimizer):
                                           plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
                                           self.max_grad_norm, self.grad_scale, skip, partials.data_ptr(), state.data_ptr()),
                     "vbx_grad_norm")
-            N.check(N.lib().vbx_adamw_step_scaled(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
-                                                  plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
-                                                  state.data_ptr(), skip), "vbx_adamw_step_scaled")
+            self._launch(plan, state, skip)
         else:
-            N.check(N.lib().vb_adamw_step(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
-                                          plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS),
-                    "vb_adamw_step")
+            self._launch(plan, None, 0)
         N.weights_changed()
         del keep
         return loss
@@ -173,7 +209,7 @@ class AdamW(Optimizer):
         coefficient, finite flag, skipped-step count) to the optimizer - the count survives a change of plan."""
         if self._grad_state is None or "partials" not in plan:
             if capturing:
-                raise RuntimeError("AdamW: the first clipped / scaled step of a plan allocates its buffers and must run "
+                raise RuntimeError(self._NAME + ": the first clipped / scaled step of a plan allocates its buffers and must run "
                                    "eagerly before a graph capture (GraphedTrainStep's warm-up does)")
             if self._grad_state is None:
                 self._grad_state = torch.zeros(N.GRAD_STATE_FLOATS, dtype=torch.float32, device=device)
@@ -183,7 +219,7 @@ class AdamW(Optimizer):
 
     def _need_state(self):
         if self._grad_state is None:
-            raise RuntimeError("AdamW: no clipped / scaled step has run yet (max_grad_norm, grad_scale and skip_nonfinite "
+            raise RuntimeError(self._NAME + ": no clipped / scaled step has run yet (max_grad_norm, grad_scale and skip_nonfinite "
                                "are all at their defaults, or step() was never called)")
         return self._grad_state
 
@@ -206,8 +242,7 @@ class AdamW(Optimizer):
         return float(self._grad_state[N.GRAD_STATE_FINITE].item()) == 0.0
 
     def _fill_table(self, plan, entries, pointers=True):
-        """Per-step columns of the launch table: gradient pointers and the hyper-parameters of this step (vectorised:
-        this runs on the host once per step, ~530 rows)."""
+        """Per-step columns of the launch table: gradient pointers and the hyper-parameters of this step."""
         tab = plan["tab"]
         keep = []
         if pointers:
@@ -215,11 +250,58 @@ class AdamW(Optimizer):
                 grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
                 keep.append(grad)
                 tab["grad"][i] = grad.data_ptr()
-        n = len(entries)
+        self._fill_hyper(plan, entries)
+        return keep
+
+    def _group_index(self, plan, entries):
+        """Index of every entry's parameter group (cached in the plan)."""
         gi = plan.get("group_index")
-        if gi is None or len(gi) != n:
+        if gi is None or len(gi) != len(entries):
             ids = {id(g): k for k, g in enumerate(self.param_groups)}
             gi = plan["group_index"] = np.array([ids[id(g)] for _p, _st, g in entries], dtype=np.int64)
+        return gi
+
+    def prepare_replay(self):
+        """Host side of one replay of a captured step (GraphedTrainStep): advances the step counts and rewrites the
+        pinned table the captured copy node reads (learning-rate schedule, bias correction). The previous replay
+        must have finished reading the table (the caller synchronises)."""
+        plan, entries = self._captured
+        for _p, st, _g in entries:
+            st["step"] += 1
+        self._fill_table(plan, entries, pointers=False)     # the gradients live at fixed addresses (arena)
+        self._stage(plan, 0)
+
+
+class AdamW(_MultiTensorOptimizer):
+    """Adam with decoupled weight decay; ``correct_bias=False`` reproduces the original BERT optimizer
+    (train_tasks.py:426). State layout (``step``, ``exp_avg``, ``exp_avg_sq``) matches pytorch-transformers, so
+    the ``.tar`` checkpoints the reference scripts write stay interchangeable.
+
+    ``max_grad_norm``, ``grad_scale`` and ``skip_nonfinite`` are those of the base class. That ``state["step"]`` advances
+    on the host also for a skipped step only matters with ``correct_bias=True``, which neither reference script uses."""
+
+    _NAME = "AdamW"
+    _SPARSE_MESSAGE = "Adam does not support sparse gradients, please consider SparseAdam instead"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
+                 max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        self._init_native(max_grad_norm, grad_scale, skip_nonfinite)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
+        super(AdamW, self).__init__(params, defaults)
+        self._init_plan()
+
+    def _fill_hyper(self, plan, entries):
+        """(vectorised: this runs on the host once per step, ~530 rows)"""
+        tab, n = plan["tab"], len(entries)
+        gi = self._group_index(plan, entries)
         groups = self.param_groups
         lr = np.array([g["lr"] for g in groups], dtype=np.float64)[gi]
         b1 = np.array([g["betas"][0] for g in groups], dtype=np.float64)[gi]
@@ -231,17 +313,113 @@ class AdamW(Optimizer):
         step_size = np.where(corr, lr * np.sqrt(1.0 - b2 ** steps) / (1.0 - b1 ** steps), lr)
         tab["step_size"], tab["beta1"], tab["beta2"] = step_size, b1, b2
         tab["eps"], tab["decay"] = eps, lr * wd
-        return keep
 
-    def prepare_replay(self):
-        """Host side of one replay of a captured step (GraphedTrainStep): advances the step counts and rewrites the
-        pinned table the captured copy node reads (learning-rate schedule, bias correction). The previous replay
-        must have finished reading the table (the caller synchronises)."""
-        plan, entries = self._captured
-        for _p, st, _g in entries:
-            st["step"] += 1
-        self._fill_table(plan, entries, pointers=False)     # the gradients live at fixed addresses (arena)
-        plan["pinned"][0].numpy()[:] = plan["tab"].view(np.uint8).reshape(-1)
+    def _launch(self, plan, state, skip):
+        args = (N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), plan["chunk_tensor"].data_ptr(),
+                plan["chunk_off"].data_ptr(), CHUNK_ELEMS)
+        if state is None:
+            N.check(N.lib().vb_adamw_step(*args), "vb_adamw_step")
+        else:
+            N.check(N.lib().vbx_adamw_step_scaled(*(args + (state.data_ptr(), skip))), "vbx_adamw_step_scaled")
+
+
+def radam_schedule(step, lr, beta1, beta2):
+    """Host side of one RAdam step for a tensor at 1-based `step`, in double: (N_sma, step_size). N_sma is the length of
+    the approximated simple moving average (rho_t of the paper); from N_sma >= 5 on the step is rectified - the adaptive
+    update scaled by r_t = sqrt((N-4)(N-2) N_max / ((N_max-4)(N_max-2) N)) and by the bias correction of the second
+    moment - before that it is SGD with (bias-corrected) momentum. The products and quotients run left to right in the
+    reference's order, so that the doubles agree to the bit."""
+    beta2_t = beta2 ** step
+    n_max = 2 / (1 - beta2) - 1
+    n_sma = n_max - 2 * step * beta2_t / (1 - beta2_t)
+    if n_sma >= 5:
+        rect = math.sqrt((1 - beta2_t) * (n_sma - 4) / (n_max - 4) * (n_sma - 2) / n_sma * n_max / (n_max - 2))
+        return n_sma, lr * rect / (1 - beta1 ** step)
+    return n_sma, lr / (1 - beta1 ** step)
+
+
+class PlainRAdam(_MultiTensorOptimizer):
+    """Rectified Adam with the constructor, the arithmetic and the state layout (``step``, ``exp_avg``, ``exp_avg_sq``) of
+    the reference's ``vilbert.optimization.PlainRAdam``, as ONE native multi-tensor launch (csrc/optimizer.hip:
+    radam_kernel). Checkpoints are interchangeable with the reference class in both directions. Every tensor's step size
+    comes from its own step count and its own group's learning rate. Parameters without a gradient are skipped and their
+    step count does not advance. ``max_grad_norm`` / ``grad_scale`` / ``skip_nonfinite`` as in the base class (the
+    reference classes have none of the three; the defaults leave them off)."""
+
+    _NAME = "PlainRAdam"
+    _SPARSE_MESSAGE = "RAdam does not support sparse gradients"
+    _EXTRA_DTYPE = _RADAM_DTYPE
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
+                 max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
+        self._init_native(max_grad_norm, grad_scale, skip_nonfinite)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        super(PlainRAdam, self).__init__(params, defaults)
+        self._init_plan()
+
+    def _schedule(self, step, group):
+        beta1, beta2 = group["betas"]
+        return radam_schedule(step, group["lr"], beta1, beta2)
+
+    def _fill_hyper(self, plan, entries):
+        """One pass in parameter-group order (RAdam's step-size cache depends on that order); the arithmetic is Python
+        floats, i.e. double."""
+        assert ctypes.sizeof(N.RAdamScalars) == _RADAM_DTYPE.itemsize
+        n = len(entries)
+        cols = np.empty((7, n), dtype=np.float64)
+        rect = np.empty(n, dtype=np.int32)
+        for i, (_p, st, group) in enumerate(entries):
+            n_sma, step_size = self._schedule(st["step"], group)
+            beta1, beta2 = group["betas"]
+            cols[:, i] = (step_size, group["weight_decay"] * group["lr"], beta1, beta2, 1 - beta1, 1 - beta2, group["eps"])
+            rect[i] = n_sma >= 5
+        extra = plan["extra"]
+        for k, name in enumerate(("step_size", "decay", "beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps")):
+            extra[name] = cols[k]
+        extra["rectified"] = rect
+
+    def _launch(self, plan, state, skip):
+        N.check(N.lib().vbo_radam_step(N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), self._extra_ptr(plan),
+                                       plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
+                                       None if state is None else state.data_ptr(), skip), "vbo_radam_step")
+
+
+class RAdam(PlainRAdam):
+    """The reference's ``vilbert.optimization.RAdam`` (``train_tasks.py --optim RAdam``) on the native launch. It differs
+    from PlainRAdam in one deliberate quirk, reproduced here because it decides real trajectories: ``self.buffer`` caches
+    ``[step, N_sma, step_size]`` in ten slots indexed by ``step % 10``, and the cached ``step_size`` already contains the
+    learning rate. Whichever tensor reaches a step count first fills the slot with ITS group's lr, and every later tensor
+    at the same step count - in this step() call or a later one - takes that step size whatever its own group's lr is.
+    train_tasks.py builds one group per parameter with task-dependent learning rates, so all of them move with the step
+    size of the first group. Weight decay is not cached: it uses each group's own ``lr * weight_decay``. The buffer is
+    not part of ``state_dict()`` (nor is it upstream): after a reload it refills on the next step."""
+
+    _NAME = "RAdam"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0,
+                 max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
+        self.buffer = [[None, None, None] for _ in range(10)]
+        super(RAdam, self).__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                    max_grad_norm=max_grad_norm, grad_scale=grad_scale, skip_nonfinite=skip_nonfinite)
+
+    def __setstate__(self, state):
+        super(RAdam, self).__setstate__(state)
+        if not hasattr(self, "buffer"):
+            self.buffer = [[None, None, None] for _ in range(10)]
+
+    def _schedule(self, step, group):
+        slot = self.buffer[int(step % 10)]
+        if step != slot[0]:
+            slot[0] = step
+            slot[1], slot[2] = super(RAdam, self)._schedule(step, group)
+        return slot[1], slot[2]
+
+
+# The classes carry the module path they have upstream, `vilbert.optimization` - the path the scripts import them from and
+# the one a whole-object pickle (`torch.save(optimizer)`) records, so that such a pickle written upstream resolves to the
+# native class here and vice versa (vilbert/utils.py does the same for the reference's logging classes). The finder in
+# vilbert/__init__.py makes `vilbert.optimization.RAdam` this very class.
+RAdam.__module__ = PlainRAdam.__module__ = "vilbert.optimization"
 
 
 class ConstantLRSchedule(LambdaLR):
