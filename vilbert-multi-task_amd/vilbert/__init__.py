@@ -56,10 +56,11 @@ attach_reference()
 # for this one name; without a checkout (the GPU-only install) the name resolves to vilbert/_optimization.py, which offers
 # the two classes alone. Lazy: nothing is imported until somebody asks for the module.
 class _RebindingLoader(object):
-    """The loader the path search found, plus the two assignments after the module body ran."""
+    """The loader the path search found, plus the assignments (`rebind(module)`) after the module body ran."""
 
-    def __init__(self, inner):
+    def __init__(self, inner, rebind):
         self._inner = inner
+        self._rebind = rebind
 
     def __getattr__(self, name):          # get_source, get_code, is_package, ...: the inner loader's
         return getattr(self._inner, name)
@@ -69,22 +70,45 @@ class _RebindingLoader(object):
 
     def exec_module(self, module):
         self._inner.exec_module(module)
-        from . import optim
-        module.RAdam, module.PlainRAdam = optim.RAdam, optim.PlainRAdam
+        self._rebind(module)
+
+
+def _rebind_optimization(module):
+    from . import optim
+    module.RAdam, module.PlainRAdam = optim.RAdam, optim.PlainRAdam
+
+
+# --- `vilbert.task_utils`: the reference's module, with its criteria and answer score on the native kernels ----------
+# train_tasks.py:41-46 takes LoadLosses / ForwardModelsTrain / ForwardModelsVal from it; those read the module globals
+# `LossMap` (the criterion objects, task_utils.py:25-28) and `compute_score_with_logits` (:618-623) at call time. The same
+# finder serves this name: the module is the reference's own file - `__file__` and every other name of it as upstream -
+# and after its body ran the two LossMap entries are instances of vilbert/task_losses.py's subclasses of the same torch
+# modules (native on fp32 HIP tensors, `super().forward` everywhere else) and the score function is task_losses'. There
+# is no stand-in: without a checkout the name stays unimportable, as the rest of the reference's data side does.
+def _rebind_task_utils(module):
+    from . import task_losses
+    module.LossMap["BCEWithLogitLoss"] = task_losses.BCEWithLogitsLoss(reduction="mean")
+    module.LossMap["CrossEntropyLoss"] = task_losses.CrossEntropyLoss()
+    module.compute_score_with_logits = task_losses.compute_score_with_logits
 
 
 class _OptimizationFinder(object):
     @staticmethod
     def find_spec(fullname, path=None, target=None):
-        if fullname != __name__ + ".optimization":
+        if fullname not in (__name__ + ".optimization", __name__ + ".task_utils"):
             return None
         from importlib.machinery import PathFinder
         from importlib.util import spec_from_file_location
         spec = PathFinder.find_spec(fullname, list(__path__))          # the reference's file, if a checkout is attached
+        if fullname == __name__ + ".task_utils":
+            if spec is None or spec.loader is None:
+                return None                                             # no checkout: the ordinary search fails as it always did
+            spec.loader = _RebindingLoader(spec.loader, _rebind_task_utils)
+            return spec
         if spec is None or spec.loader is None:
             spec = spec_from_file_location(fullname, _os.path.join(_os.path.dirname(_os.path.abspath(__file__)),
                                                                    "_optimization.py"))
-        spec.loader = _RebindingLoader(spec.loader)
+        spec.loader = _RebindingLoader(spec.loader, _rebind_optimization)
         return spec
 
 

@@ -365,6 +365,15 @@ OPT_SIGNATURES = {
     "vbo_radam_step": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _I32]),
 }
 
+# include/vilbert_hip_tasks.h (loss and answer score of the fine-tuning heads; prefix vbt_), mirrored one to one (checked by
+# tests/test_task_losses.py)
+TASK_SIGNATURES = {
+    "vbt_bce_workspace": (_I64, [_I64, _I32]),
+    "vbt_bce_fwd": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P]),
+    "vbt_bce_bwd": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _I64]),
+    "vbt_argmax_pick": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _P, _I64]),
+}
+
 _lib = None
 
 
@@ -377,7 +386,8 @@ def lib():
                 "libvilbert_hip.so not found at %s - build it with `python -c 'import __graft_entry__ as g; "
                 "g.build()'` (or `make -C vilbert-multi-task_amd/csrc`). There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
+                                  + list(TASK_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

@@ -10,6 +10,7 @@ import itertools
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import arena as _arena
@@ -517,6 +518,22 @@ class KLDivFn(torch.autograd.Function):
     def backward(ctx, grad_loss):
         scores, target, lse, tsum = ctx.saved_tensors
         return ops.kl_bwd(grad_loss, scores, target, lse, tsum, ctx.divisor), None, None
+
+
+class BCEWithLogitsFn(torch.autograd.Function):
+    """nn.BCEWithLogitsLoss(reduction="mean") - reference task_utils.py:25-28, 325-374. Nothing but the two operands is
+    saved (the backward recomputes the sigmoid); the target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, target):
+        ctx.save_for_backward(logits, target)
+        return ops.bce_fwd(logits, target)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        logits, target = ctx.saved_tensors
+        return ops.bce_bwd(grad_loss, logits, target), None
 
 
 class CastFn(Function):

@@ -950,3 +950,62 @@ def kl_bwd(grad_loss, scores, target, lse, tsum, divisor):
                               N.dev_f32(tsum, "kl_div tsum"), N.dev_f32(grad_loss, "kl_div grad"), dh,
                               d.data_ptr(), n, dd), "vb_kl_bwd")
     return d
+
+
+def _task_rows(t):
+    """[rows, n] view of a head output or target for the vbt_ entry points (csrc/task_loss.hip), never a copy of a
+    row-strided 2-D view: a [B, R, 1] region logit is the view [B, R], any other shape is flattened to [-1, last dim]
+    (copied only if it is not contiguous). Returns (view, row stride)."""
+    if t.dim() == 3 and t.shape[2] == 1:
+        t = t.squeeze(2)
+    if not _row_strided(t):
+        t = _contig(t)
+        t = t.view(-1, t.shape[-1]) if t.dim() >= 1 else t.view(1, 1)
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def bce_fwd(logits, target):
+    """nn.BCEWithLogitsLoss(reduction="mean")(logits, target): fp32 tensors of one shape. Two launches at most, no host
+    synchronisation, bit-identical from run to run (per-block partial sums added in order). Returns the 0-dim loss."""
+    if logits.shape != target.shape or logits.numel() == 0:
+        raise RuntimeError("bce_with_logits: expected non-empty logits and target of the same shape")
+    x, ld = _task_rows(logits)
+    t, ldt = _task_rows(target)
+    rows, n = x.shape
+    lib = N.lib()
+    out = torch.empty(1 + int(lib.vbt_bce_workspace(rows, n)), dtype=torch.float32, device=x.device)   # {loss, partials}
+    N.check(lib.vbt_bce_fwd(N.stream_ptr(), rows, n, N.dev_f32(x, "bce_with_logits logits"), ld,
+                            N.dev_f32(t, "bce_with_logits target"), ldt, out.data_ptr() + 4, out.data_ptr()), "vbt_bce_fwd")
+    return out[0]
+
+
+def bce_bwd(grad_loss, logits, target):
+    """Gradient of bce_fwd with respect to the logits, in the logits' shape; a row-strided 2-D view keeps its row stride
+    (the padding is not written)."""
+    x, ld = _task_rows(logits)
+    t, ldt = _task_rows(target)
+    rows, n = x.shape
+    grad_loss = _contig(grad_loss).reshape(1)
+    d = torch.empty(rows, ld, dtype=torch.float32, device=x.device)[:, :n]
+    N.check(N.lib().vbt_bce_bwd(N.stream_ptr(), rows, n, N.dev_f32(x, "bce_with_logits logits"), ld,
+                                N.dev_f32(t, "bce_with_logits target"), ldt, N.dev_f32(grad_loss, "bce_with_logits grad"),
+                                d.data_ptr(), ld), "vbt_bce_bwd")
+    return d if d.shape == logits.shape else d.reshape(logits.shape)
+
+
+def argmax_pick(logits, labels, want_dense=False):
+    """Per row of the [rows, n] view: idx = lowest index of the maximum of the logits (a NaN counts as the maximum),
+    picked = labels[row, idx]; with want_dense also the matrix compute_score_with_logits returns (zeros, `picked` at idx)
+    in the labels' shape. One launch. Returns (idx int64 [rows], picked fp32 [rows], dense or None)."""
+    if logits.shape != labels.shape or logits.numel() == 0:
+        raise RuntimeError("argmax_pick: expected non-empty logits and labels of the same shape")
+    x, ld = _task_rows(logits)
+    l, ldl = _task_rows(labels)
+    rows, n = x.shape
+    idx = torch.empty(rows, dtype=torch.int64, device=x.device)
+    picked = torch.empty(rows, dtype=torch.float32, device=x.device)
+    dense = torch.empty(labels.shape, dtype=torch.float32, device=x.device) if want_dense else None   # every element is written
+    N.check(N.lib().vbt_argmax_pick(N.stream_ptr(), rows, n, N.dev_f32(x, "argmax_pick logits"), ld,
+                                    N.dev_f32(l, "argmax_pick labels"), ldl, idx.data_ptr(), picked.data_ptr(),
+                                    dense.data_ptr() if want_dense else None, n), "vbt_argmax_pick")
+    return idx, picked, dense
