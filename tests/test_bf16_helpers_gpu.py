@@ -1,4 +1,4 @@
-"""The helper kernels of the bf16 training stream, called directly (csrc/gemm_bf16.hip "small kernels", layernorm.hip): the
+"""The helper kernels of the bf16 training stream, called directly (csrc/bf16_helpers.hip, layernorm.hip): the
 casts that carry every value across the fp32 / bf16 border, the weight shadows, the bf16 column sum and the bf16 LayerNorm
 at the edges of its shape range. The stream's own tests (test_bf16_stream_gpu.py) reach them only at the model's widths.
 

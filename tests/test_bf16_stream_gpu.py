@@ -86,6 +86,41 @@ def test_linear16_forward_dgrad_wgrad_match_float64(M, nseg, seg_n, K):
              "wgrad into a fresh buffer")
 
 
+# The block-to-tile map the persistent kernels share (csrc/persistent_map.h), one launch per branch the cases above do not
+# reach (K = 64: one K tile per output tile, so a launch is all tile boundaries). Default block choice (plan_hb): half-size
+# 128 x 128 tiles up to 128 full-size tiles, 256 x 128 beyond.
+@pytest.mark.parametrize("M,N,K", [(300, 384, 64),      # 9 half tiles: a round that is no multiple of 8, dealt block by block
+                                   (1024, 1024, 64),    # 64 half tiles in 8 x 8: the 4 x 8 patches
+                                   (4352, 1024, 64),    # 136 full tiles, 17 tile rows: XCD runs of 17, walked row by row
+                                   (5120, 1024, 64),    # 160 full tiles in 20 x 8: XCD runs of 20 over 4 x 8 patches
+                                   (8448, 1024, 64)])   # 264 full tiles: a second round of 8
+def test_linear16_forward_on_every_branch_of_the_tile_map(M, N, K):
+    from vilbert import ops16
+    x, w, b = _rand(M, K, seed=1).to(BF16), _rand(N, K, seed=2, scale=0.05), _rand(N, seed=3)
+    w16 = w.to(BF16).double()
+    y, _ = ops16.linear_fwd(x.to(DEV), [w.to(DEV)], [b.to(DEV)])
+    _close16(y, x.double() @ w16.t() + b.double(), x.double().abs() @ w16.abs().t() + 1.0, "forward %d x %d x %d" % (M, N, K))
+
+
+@pytest.mark.parametrize("M,nseg,seg_n,K", [(200, 1, 256, 128),     # one output tile, 4 contraction splits, grid rounded up to 8
+                                            (1100, 3, 256, 768)])   # 18 tiles of three stacked segments, ragged last K tile
+def test_wgrad16_units_small_launches_twice_bit_identical(M, nseg, seg_n, K):
+    from vilbert import _native, ops16
+    assert _native.deterministic_enabled(), "the deterministic setting (default on) is what makes two runs comparable"
+    x, dy = _rand(M, K, seed=1).to(BF16), _rand(M, nseg * seg_n, seed=4).to(BF16)
+    runs = []
+    for _ in range(2):
+        dws, dbs = ops16.linear_bwd_weight(dy.to(DEV), x.to(DEV), nseg, seg_n, [True] * nseg)
+        torch.cuda.synchronize()
+        runs.append([t.clone() for t in dws + dbs])
+    for a, c in zip(*runs):
+        assert torch.equal(a, c), "bf16 weight gradient differs between two runs of the same launch"
+    for s in range(nseg):
+        seg = dy[:, s * seg_n:(s + 1) * seg_n].double()
+        _close16(runs[0][s], seg.t() @ x.double(), seg.abs().t() @ x.double().abs() + 1.0, "wgrad %d" % s)
+        _close16(runs[0][nseg + s], seg.sum(0), seg.abs().sum(0) + 1.0, "bias grad %d" % s)
+
+
 def test_weight_shadows_follow_the_parameters():
     from vilbert import _native, ops16
     w = torch.nn.Parameter(_rand(256, 128, seed=1).to(DEV))

@@ -93,7 +93,10 @@ def _launch(xm, wm, M, N, K, bias=None, residual=None, act=None, out="f32"):
 
 
 SHAPES = [(256, 128, 128), (300, 768, 768), (77, 128, 256), (1, 256, 128), (640, 1024, 2048), (257, 3072, 768),
-          (1000, 384, 1024), (2304, 1024, 384), (9216, 768, 768)]
+          (1000, 384, 1024), (2304, 1024, 384), (9216, 768, 768),
+          # the shared tile map (csrc/persistent_map.h) beyond one tile per block: 136 tiles in 17 rows (XCD runs, row by row),
+          # 160 tiles in 20 x 8 (4 x 8 patches), 264 tiles (a second round of 8)
+          (4352, 1024, 128), (5120, 1024, 128), (8448, 1024, 128)]
 
 
 @pytest.mark.parametrize("M,N,K", SHAPES)

@@ -1,5 +1,5 @@
 // fp32 -> bf16, round to nearest even: the ONE place every bf16 store of the library takes its rounding from (the GEMM
-// epilogues and cast / shadow kernels of gemm_bf16.hip, layernorm.hip, mx8.hip, attention.hip
+// epilogues of gemm_bf16.hip, the cast / shadow kernels of bf16_helpers.hip, layernorm.hip, mx8.hip, attention.hip
 // in its bf16 build, attention_mx.hip). No HIP header and no device state. One name, two bodies with one contract:
 //   * device code for gfx950 - every kernel of the library - is the hardware convert v_cvt_pk_bf16_f32;
 //   * host code, and device code for any other architecture, is the integer add-and-shift the kernels used to carry in

@@ -10,7 +10,7 @@
 //   wgrad_bf16_kernel  dW[N, K] += dY[M, N]^T X[M, K]              contraction over the ROWS of both operands: the tiles land
 //                      in LDS row-major (LDS-DMA) and the MFMA fragments are fetched with ds_read_b64_tr_b16, gfx950's
 //                      transposing LDS read (4 x 16 block per 16 lanes -> each lane 4 consecutive rows of one column)
-//   weight_shadow_kernel, cast kernels, colsum (bias gradient)
+// (the casts, the weight shadows and the stand-alone column sums of the path: bf16_helpers.hip)
 //
 // Both GEMM kernels are the persistent skeleton of mx8.hip (its byte geometry is identical: a K tile of 64 bf16 = 128 bytes
 // per row): ONE block per CU = 8 MFMA waves in a 4 x 2 grid (wave tile 64 x 64 = 2 x 2 MFMA tiles of 32 x 32, block tile
@@ -20,7 +20,9 @@
 // register sets: step s multiplies set s & 1 while set (s + 1) & 1 is read from LDS; the barrier sits between steps 2 and 3,
 // after the last read of the stage.
 #include "det_workspace.h"
+#include "gemm_bf16_plan.h"
 #include "gemm_core.h"
+#include "persistent_map.h"
 #include <type_traits>
 
 namespace {
@@ -33,7 +35,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
 
-constexpr int HB_BM = 256, HB_BN = 128, HB_BK = 64, HB_S = 3;
+constexpr int HB_S = 3;                         // (HB_BM = 256, HB_BN = 128, HB_BK = 64: gemm_bf16_plan.h)
 constexpr int HB_ROWB = 2 * HB_BK;              // bytes of one tile row (NT kernel): 128
 constexpr int HB_A = HB_BM * HB_ROWB;           // 32,768 bytes
 constexpr int HB_B = HB_BN * HB_ROWB;           // 16,384
@@ -47,7 +49,7 @@ constexpr int HB_MFMA_WAVES = 8, HB_THREADS = 64 * (HB_MFMA_WAVES + 2 * HB_LW);
 
 // Block shapes of the NT kernel. HbFull: the geometry above, ONE block per CU. HbHalf: 128 x 128 tiles, 4 MFMA waves (2 x 2) + one
 // loader wave per operand, a 2-stage ring of 32 KiB stages = 64 KiB, so that TWO independent blocks share a CU. Built to hide
-// one block's epilogue under the other's MFMAs; measured, that only pays for SMALL launches (see launch_hb).
+// one block's epilogue under the other's MFMAs; measured, that only pays for SMALL launches (see plan_hb).
 template <int BM_, int S_, int LW_>
 struct HbCfg {
     static constexpr int BM = BM_, S = S_, LW = LW_;
@@ -59,28 +61,12 @@ struct HbCfg {
 using HbFull = HbCfg<256, 3, 2>;
 using HbHalf = HbCfg<128, 2, 1>;
 
-__device__ __forceinline__ unsigned short bf16_rne(float v) { return (unsigned short)vb_bf16_round(v); }
 __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return vb_bf16_pack(lo, hi); }
 __device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
-// one LDS-DMA: LDS[lds + 16 lane] <- *(base + off[lane]), wave-uniform 64-bit base + per-lane 32-bit byte offset
-__device__ __forceinline__ void hb_glds16(unsigned off, const void* base, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
 template <int N>
 __device__ __forceinline__ void hb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-// tile of block `b` in round `it`: the 32 blocks of an XCD (b % 8) work on a 4 x 8 patch of tiles where the tile grid allows
-// it, so that they share A / W panels in their L2 (mx8.hip: mx_tile_of / mx_origin)
-__device__ __forceinline__ int hb_tile_of(int b, int it, int grid, int tiles) {
-    const int base = it * grid;
-    const int n = min(grid, tiles - base);
-    if (n <= 0) return -1;
-    if ((n & 7) != 0) return b < n ? base + b : -1;
-    const int per = n >> 3, x = b & 7, j = b >> 3;
-    return j < per ? base + x * per + j : -1;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // NT kernel
@@ -112,19 +98,12 @@ struct HbP {
                  // 8 = no epilogue
 };
 
+// first row / column of the output tile block `b` works on in round `it` (persistent_map.h); false = none
 __device__ __forceinline__ bool hb_origin(const HbP& p, int b, int it, int grid, int& m0, int& n0) {
-    const int t = hb_tile_of(b, it, grid, p.tiles);
+    const int t = tile_of(b, it, grid, p.tiles);
     if (t < 0) return false;
-    const int tiles_m = p.tiles / p.tiles_n;
     int r, c;
-    if ((p.tiles_n & 7) == 0 && (tiles_m & 3) == 0) {
-        const int patch = t >> 5, w = t & 31, pcols = p.tiles_n >> 3;
-        r = (patch / pcols) * 4 + (w >> 3);
-        c = (patch % pcols) * 8 + (w & 7);
-    } else {
-        r = t / p.tiles_n;
-        c = t % p.tiles_n;
-    }
+    tile_rc(t, p.tiles, p.tiles_n, r, c);
     m0 = r * p.bm;
     n0 = c * HB_BN;
     return true;
@@ -162,7 +141,7 @@ __device__ __forceinline__ void hb_loader(const HbP& p, const unsigned lds0, con
         const unsigned l = lds0 + (unsigned)stage_w * HB_STAGE;
         if (!(p.flags & 1)) {
 #pragma unroll
-            for (int i = 0; i < ND; ++i) hb_glds16(off[i], base, l + REG + 1024u * (HB_LW * i + widx));
+            for (int i = 0; i < ND; ++i) glds16(off[i], base, l + REG + 1024u * (HB_LW * i + widx));
         }
         base += HB_BK;
         stage_w = stage_w == HB_S - 1 ? 0 : stage_w + 1;
@@ -194,7 +173,7 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::PER_CU == 1 ? 1 : 3) void gemm_b
     const int nk = p.K / HB_BK;
     const int b = blockIdx.x, grid = gridDim.x;
     int rounds = 0;
-    while (rounds * grid < p.tiles && hb_tile_of(b, rounds, grid, p.tiles) >= 0) ++rounds;
+    while (rounds * grid < p.tiles && tile_of(b, rounds, grid, p.tiles) >= 0) ++rounds;
     if (rounds == 0) return;
     if (Cfg::PER_CU == 2 && (p.flags & 16) && b >= grid / 2) {
         // laboratory: the second block of a CU starts half an output tile late, so that the two are never in their epilogues
@@ -379,38 +358,39 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::PER_CU == 1 ? 1 : 3) void gemm_b
     }
 }
 
-// persistent blocks per launch (VB_BF16_GRID, a multiple of 8, default = the 256 CUs): with fewer, two launches of
-// different streams share the chip side by side instead of one after the other
-inline int hb_grid_limit() {
-    static const int g = [] { const int v = vb_env_int("VB_BF16_GRID", 256); return v >= 8 && v <= 256 ? v / 8 * 8 : 256; }();
-    return g;
+// the one Bf16Knobs instance (gemm_bf16_plan.h), filled from the environment at the first launch
+const Bf16Knobs& bf16_knobs() {
+    static const Bf16Knobs kn = [] {
+        Bf16Knobs k;
+        const int g = vb_env_int("VB_BF16_GRID", 256);
+        k.grid_limit = g >= 8 && g <= 256 ? g / 8 * 8 : 256;
+        k.half = vb_env_int("VB_BF16_HALF", 1);
+        k.t_k = (float)vb_env_float("VB_BF16_WG_TK", 1.0);
+        k.t_e = (float)vb_env_float("VB_BF16_WG_TE", 0.12);
+        k.t_d = (float)vb_env_float("VB_BF16_WG_TD", 0.04);
+        return k;
+    }();
+    return kn;
 }
 
 template <int OUT, int EPI, class Cfg>
-int launch_hb_cfg(hipStream_t st, HbP p) {
+int launch_hb_cfg(hipStream_t st, HbP p, const HbPlan& pl) {
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<OUT, EPI, Cfg>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::LDS);
     if (attr != hipSuccess) return (int)attr;
-    p.bm = Cfg::BM;
-    p.tiles = ((p.M + Cfg::BM - 1) / Cfg::BM) * p.tiles_n;
-    const int slots = hb_grid_limit() * Cfg::PER_CU;
-    const int grid = p.tiles < slots ? p.tiles : slots;
-    hipLaunchKernelGGL((gemm_bf16_kernel<OUT, EPI, Cfg>), dim3(grid), dim3(Cfg::THREADS), Cfg::LDS, st, p);
+    p.bm = pl.bm;
+    p.tiles = pl.tiles;
+    hipLaunchKernelGGL((gemm_bf16_kernel<OUT, EPI, Cfg>), dim3(pl.grid), dim3(Cfg::THREADS), Cfg::LDS, st, p);
     VB_LAUNCH_CHECK();
     return 0;
 }
 
-// VB_BF16_HALF: 0 = always the full-size block, 2 = always two half-size blocks per CU, 1 (default) = the half-size blocks for
-// launches of at most 128 full-size tiles (the per-GPU batch 64 shapes: 80 tiles on 256 CUs become 160 blocks - 23.5 -> 16.6 us
-// at 2368 x 1024 x 1024). Everywhere else the half-size block LOSES (profiles/r05_bf16_half_blocks.txt): a 128 x 128 tile
-// reads a third more operand bytes per FLOP through L2 / LDS-DMA, and the main loop alone falls from ~1.0 PF to 0.62 - 0.74 PF -
-// more than the overlapped epilogues win back (q|k|v forward 44.8 -> 67.7 us).
+// full-size or half-size blocks, and how many: plan_hb
 template <int OUT, int EPI>
 int launch_hb(hipStream_t st, const HbP& p) {
-    static const int half = vb_env_int("VB_BF16_HALF", 1);
-    const int tiles_full = ((p.M + 255) / 256) * p.tiles_n;
-    const bool use_half = half == 2 || (half == 1 && tiles_full <= 128);
-    return use_half ? launch_hb_cfg<OUT, EPI, HbHalf>(st, p) : launch_hb_cfg<OUT, EPI, HbFull>(st, p);
+    const HbPlan pl = plan_hb(p.M, p.tiles_n, bf16_knobs());
+    static_assert(HbHalf::BM == 128 && HbHalf::PER_CU == 2 && HbFull::BM == 256 && HbFull::PER_CU == 1, "plan_hb's two shapes");
+    return pl.bm == HbHalf::BM ? launch_hb_cfg<OUT, EPI, HbHalf>(st, p, pl) : launch_hb_cfg<OUT, EPI, HbFull>(st, p, pl);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -449,19 +429,9 @@ struct HwP {
     int n_valid;                    // rows of a segment's dW (and entries of its db) that exist: the tiles cover cseg >= n_valid rows
 };
 
-// unit of block `b` in its i-th round: the 32 blocks of an XCD (b % 8) take CONSECUTIVE units - the same contraction split and
-// neighbouring output tiles - so that the row range of dY / X they stream is shared in their L2 (hb_tile_of's map)
-// (grid = a multiple of 8; any unit count: XCD x takes the units [x per, (x + 1) per) of the round, per = ceil(n / 8))
-__device__ __forceinline__ int hw_unit_of(int b, int i, int grid, int units) {
-    const int base = i * grid;
-    const int n = min(grid, units - base);
-    if (n <= 0) return -1;
-    const int per = (n + 7) >> 3, x = b & 7, j = b >> 3;
-    const int idx = x * per + j;
-    return (j < per && idx < n) ? base + idx : -1;
-}
+// output tile origin and contraction range of the unit block `b` works on in its i-th round (persistent_map.h: unit_of)
 __device__ __forceinline__ void hw_unit(const HwP& p, int b, int i, int grid, int& n0, int& k0, int& kt0, int& nk) {
-    const int u = hw_unit_of(b, i, grid, p.units);
+    const int u = unit_of(b, i, grid, p.units);
     const int split = u / p.tiles, t = u - split * p.tiles;
     n0 = (t / p.tiles_k) * HB_BM;
     k0 = (t % p.tiles_k) * HB_BN;
@@ -504,7 +474,7 @@ __device__ __forceinline__ void hw_loader(const HwP& p, const unsigned lds0, con
         if (p.flags & 1) {
         } else if (rows_left >= HB_BK) {
 #pragma unroll
-            for (int i = 0; i < ND; ++i) hb_glds16(off[i], base, l + REG + 1024u * (HB_LW * i + widx));
+            for (int i = 0; i < ND; ++i) glds16(off[i], base, l + REG + 1024u * (HB_LW * i + widx));
         } else {
             // the last contraction tile of a ragged M: rows past the end are fetched from the last real row (finite
             // data; the MFMA waves zero the dY fragment elements of those rows)
@@ -512,7 +482,7 @@ __device__ __forceinline__ void hw_loader(const HwP& p, const unsigned lds0, con
             for (int i = 0; i < ND; ++i) {
                 const int m = RPD * (HB_LW * i + widx) + sub;
                 const unsigned o = (unsigned)((long)min(m, rows_left - 1) * ld * 2 + 16 * (cp ^ ((m & 3) << 2)));
-                hb_glds16(o, base, l + REG + 1024u * (HB_LW * i + widx));
+                glds16(o, base, l + REG + 1024u * (HB_LW * i + widx));
             }
         }
         base += (long)HB_BK * ld;
@@ -538,7 +508,7 @@ __global__ __launch_bounds__(HB_THREADS) void wgrad_bf16_kernel(const HwP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int b = blockIdx.x, grid = gridDim.x;
     int n_units = 0;
-    while (n_units * grid < p.units && hw_unit_of(b, n_units, grid, p.units) >= 0) ++n_units;
+    while (n_units * grid < p.units && unit_of(b, n_units, grid, p.units) >= 0) ++n_units;
     if (n_units == 0) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= HB_MFMA_WAVES) {
@@ -698,7 +668,7 @@ __global__ __launch_bounds__(HB_THREADS) void wgrad_bf16_kernel(const HwP p) {
         if (p.flags & 8) continue;
         const int seg = n0 / p.cseg;
         if (p.ws != nullptr) {
-            const int u = hw_unit_of(b, ui, grid, p.units);      // = split * tiles + tile
+            const int u = unit_of(b, ui, grid, p.units);      // = split * tiles + tile
             f32x4* __restrict__ w = reinterpret_cast<f32x4*>(p.ws) + ((long)u * 8 + wave) * (4 * 4 * 64) + lane;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -770,151 +740,6 @@ __global__ __launch_bounds__(256) void wgrad_bf16_reduce_kernel(const HwP p) {
         for (int s = 1; s < p.splits; ++s) a += p.ws_b[(long)s * p.N + n];
         p.bias[seg][n - (long)seg * p.cseg] += a;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// small kernels
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cast_f32_bf16_kernel(long n8, const float* __restrict__ x, unsigned short* __restrict__ y,
-                                                            long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n8) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(x + 8 * i), c = *reinterpret_cast<const f32x4*>(x + 8 * i + 4);
-        *reinterpret_cast<v4i*>(y + 8 * i) = v4i{(int)pack_bf16(a[0], a[1]), (int)pack_bf16(a[2], a[3]), (int)pack_bf16(c[0], c[1]),
-                                                 (int)pack_bf16(c[2], c[3])};
-    } else if (i == n8) {
-        for (long e = 8 * n8; e < n; ++e) y[e] = bf16_rne(x[e]);
-    }
-}
-
-// fp32 [rows][n] (row stride ldx) -> bf16 [rows][ldy], columns n .. ldy - 1 zero-filled: the padded bf16 operand of a weight
-// gradient whose output width is not a tile multiple (the 30,522-wide MLM decoder: 30,720 = 120 x 256)
-__global__ __launch_bounds__(256) void cast_rows_f32_bf16_kernel(long rows, int n, const float* __restrict__ x, long ldx,
-                                                                 unsigned short* __restrict__ y, long ldy) {
-    const long chunks = ldy / 8;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= rows * chunks) return;
-    const long r = i / chunks;
-    const int c = (int)(i % chunks) * 8;
-    const float* __restrict__ xp = x + r * ldx + c;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-    if (c + 8 <= n) {
-        a = *reinterpret_cast<const f32x4*>(xp);
-        b = *reinterpret_cast<const f32x4*>(xp + 4);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (c + e < n) a[e] = xp[e];
-            if (c + 4 + e < n) b[e] = xp[4 + e];
-        }
-    }
-    *reinterpret_cast<v4i*>(y + r * ldy + c) = v4i{(int)pack_bf16(a[0], a[1]), (int)pack_bf16(a[2], a[3]), (int)pack_bf16(b[0], b[1]),
-                                                   (int)pack_bf16(b[2], b[3])};
-}
-
-__global__ __launch_bounds__(256) void cast_bf16_f32_kernel(long n8, const unsigned short* __restrict__ x, float* __restrict__ y,
-                                                            long n) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n8) {
-        const v4i w = *reinterpret_cast<const v4i*>(x + 8 * i);
-        *reinterpret_cast<f32x4*>(y + 8 * i) = f32x4{bf16_lo(w[0]), bf16_hi(w[0]), bf16_lo(w[1]), bf16_hi(w[1])};
-        *reinterpret_cast<f32x4*>(y + 8 * i + 4) = f32x4{bf16_lo(w[2]), bf16_hi(w[2]), bf16_lo(w[3]), bf16_hi(w[3])};
-    } else if (i == n8) {
-        for (long e = 8 * n8; e < n; ++e) y[e] = __uint_as_float((unsigned)x[e] << 16);
-    }
-}
-
-// fp32 master weight [rows, cols] -> bf16 shadow rows (w16 [rows, ld16]) AND its transpose (wt16 [cols, ldt], written at
-// column offset col_off = the row offset of this segment inside a stacked weight); 64 x 64 tiles through LDS
-__global__ __launch_bounds__(256) void weight_shadow_kernel(int rows, int cols, const float* __restrict__ w, long ldw,
-                                                            unsigned short* __restrict__ w16, long ld16,
-                                                            unsigned short* __restrict__ wt16, long ldt) {
-    __shared__ unsigned short tile[64][66];
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    const int tr = threadIdx.x >> 4, tc = (threadIdx.x & 15) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = tr + 16 * i;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(w + (long)(r0 + row) * ldw + c0 + tc);
-        const unsigned lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
-        if (w16 != nullptr) *reinterpret_cast<uint2*>(w16 + (long)(r0 + row) * ld16 + c0 + tc) = uint2{lo, hi};
-        tile[row][tc] = (unsigned short)lo; tile[row][tc + 1] = (unsigned short)(lo >> 16);
-        tile[row][tc + 2] = (unsigned short)hi; tile[row][tc + 3] = (unsigned short)(hi >> 16);
-    }
-    __syncthreads();
-    if (wt16 == nullptr) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = tr + 16 * i;      // row of the transposed tile
-        const unsigned lo = (unsigned)tile[tc][col] | ((unsigned)tile[tc + 1][col] << 16);
-        const unsigned hi = (unsigned)tile[tc + 2][col] | ((unsigned)tile[tc + 3][col] << 16);
-        *reinterpret_cast<uint2*>(wt16 + (long)(c0 + col) * ldt + r0 + tc) = uint2{lo, hi};
-    }
-}
-
-// the same for EVERY registered weight in one launch (once per optimizer step): block b finds its segment in the table by
-// bisection over the segments' first tile
-__global__ __launch_bounds__(256) void weight_shadow_multi_kernel(int n_segs, const vb_shadow_seg* __restrict__ tab) {
-    __shared__ unsigned short tile[64][66];
-    int lo = 0, hi = n_segs - 1;
-    const long b = blockIdx.x;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[mid].tile0 <= b) lo = mid; else hi = mid - 1;
-    }
-    const vb_shadow_seg sg = tab[lo];
-    const int t = (int)(b - sg.tile0), tiles_c = sg.cols >> 6;
-    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
-    const int tr = threadIdx.x >> 4, tc = (threadIdx.x & 15) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = tr + 16 * i;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(sg.w + (long)(r0 + row) * sg.cols + c0 + tc);
-        const unsigned lo2 = pack_bf16(v[0], v[1]), hi2 = pack_bf16(v[2], v[3]);
-        *reinterpret_cast<uint2*>(sg.w16 + (long)(r0 + row) * sg.ld16 + c0 + tc) = uint2{lo2, hi2};
-        tile[row][tc] = (unsigned short)lo2; tile[row][tc + 1] = (unsigned short)(lo2 >> 16);
-        tile[row][tc + 2] = (unsigned short)hi2; tile[row][tc + 3] = (unsigned short)(hi2 >> 16);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = tr + 16 * i;
-        const unsigned lo2 = (unsigned)tile[tc][col] | ((unsigned)tile[tc + 1][col] << 16);
-        const unsigned hi2 = (unsigned)tile[tc + 2][col] | ((unsigned)tile[tc + 3][col] << 16);
-        *reinterpret_cast<uint2*>(sg.wt16 + (long)(c0 + col) * sg.ldt + r0 + tc) = uint2{lo2, hi2};
-    }
-}
-
-// column sums of a bf16 [rows, cols] matrix (bias gradient): stage 1 - a block owns 256 columns x one row slab, a thread 4
-// columns of every fourth row, waves summed through LDS, one partial row per slab; stage 2 - the slabs in order
-// (deterministic). out: ADDED into (the gradient arena semantics of the weight gradients).
-constexpr int CS_SLABS = 64;
-__global__ __launch_bounds__(256) void colsum16_kernel(long rows, int cols, const unsigned short* __restrict__ x, long ldx,
-                                                       float* __restrict__ part) {
-    __shared__ f32x4 red[3][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = blockIdx.x * 256 + 4 * lane;
-    const long per = (rows + CS_SLABS - 1) / CS_SLABS;
-    const long lo = blockIdx.y * per, hi = min(rows, lo + per);
-    f32x4 s = {0.f, 0.f, 0.f, 0.f};
-    if (col < cols)
-        for (long r = lo + wave; r < hi; r += 4) {
-            const uint2 w = *reinterpret_cast<const uint2*>(x + r * ldx + col);
-            s += f32x4{bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y)};
-        }
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && col < cols) {
-        s += red[0][lane]; s += red[1][lane]; s += red[2][lane];
-        *reinterpret_cast<f32x4*>(part + (long)blockIdx.y * cols + col) = s;
-    }
-}
-__global__ __launch_bounds__(256) void colsum16_finish_kernel(int cols, const float* __restrict__ part, float* __restrict__ out) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= cols) return;
-    float s = 0.f;
-    for (int i = 0; i < CS_SLABS; ++i) s += part[(long)i * cols + c];
-    out[c] += s;
 }
 
 }  // namespace
@@ -995,42 +820,18 @@ extern "C" int vb_wgrad_bf16(void* stream, const vb_wgrad_bf16_args* a) {
     if (a->n_valid < 0 || a->n_valid > a->seg_n || (a->n_valid != 0 && a->n_valid != a->seg_n && a->nseg != 1)) return VB_E_BADARG;
     p.n_valid = a->n_valid > 0 ? a->n_valid : a->seg_n;
     p.tiles_k = p.K / HB_BN;
-    p.tiles = (p.N / HB_BM) * p.tiles_k;
-    p.nkt = (p.M + HB_BK - 1) / HB_BK;
-    // Contraction splits by a time model (measured with the laboratory flags, profiles/r05_bf16_lab_ablations.txt): a unit's
-    // main loop costs ~1.0 us per contraction tile, its epilogue - 128 KiB of fp32 atomics that execute at the memory side,
-    // ~1.7 TB/s for the whole chip - ~0.075 us per unit IN FLIGHT ANYWHERE (0.12 in the model: in the step, where other streams compete for the memory side, fewer splits measured +0.7 %); rounds of 256 units. More splits shorten the main
-    // loop and lengthen the atomics: the first version's "fill two rounds" rule spent 30 - 50 % of a launch in atomics.
-    static const float t_k = (float)vb_env_float("VB_BF16_WG_TK", 1.0);
-    static const float t_e = (float)vb_env_float("VB_BF16_WG_TE", 0.12);
-    // deterministic form: a unit's 128 KiB leave as plain 16-byte stores (t_d per unit), and the reduce pass reads every
-    // partial once and updates dW: (splits + 2) x 4 N K bytes at ~3.5 TB/s + its launch
-    static const float t_d = (float)vb_env_float("VB_BF16_WG_TD", 0.04);
     hipStream_t st = static_cast<hipStream_t>(stream);
+    // splits, grid and atomics or the deterministic slice: plan_hw
     size_t slice_bytes = 0;
     float* slice = det_on() ? det_slice(st, &slice_bytes) : nullptr;
-    const size_t per_split = ((size_t)p.tiles * 32768 + (size_t)p.N) * sizeof(float);
-    int best = 1;
-    float best_t = 1e30f;
-    for (int sp = 1; sp <= p.nkt && sp <= 64; ++sp) {
-        const int per = (p.nkt + sp - 1) / sp, real = (p.nkt + per - 1) / per;
-        if (real != sp) continue;
-        const long units = (long)p.tiles * sp;
-        float t = (float)((units + 255) / 256) * (per * t_k + 2.0f);
-        if (slice != nullptr) {
-            if ((size_t)sp * per_split > slice_bytes) continue;
-            t += units * t_d + 3.0f + (float)(sp + 2) * (4.0f * p.N * p.K) / 3.5e6f;
-        } else {
-            t += units * t_e;
-        }
-        if (t < best_t) { best_t = t; best = sp; }
-    }
-    if (best_t >= 1e30f) slice = nullptr;          // (not even one split fits the slice)
-    if (det_on() && slice == nullptr) det_fallback();
-    p.kt_per_split = (p.nkt + best - 1) / best;
-    p.splits = (p.nkt + p.kt_per_split - 1) / p.kt_per_split;
-    p.units = p.tiles * p.splits;
-    if (slice != nullptr) {
+    const HwPlan pl = plan_hw(p.M, p.N, p.K, slice != nullptr ? slice_bytes : 0, bf16_knobs());
+    if (det_on() && !pl.use_ws) det_fallback();   // pl.fallback (the slice is too small), or the stream has no slice
+    p.tiles = pl.tiles;
+    p.nkt = pl.nkt;
+    p.kt_per_split = pl.kt_per_split;
+    p.splits = pl.splits;
+    p.units = pl.units;
+    if (pl.use_ws) {
         p.ws = slice;
         p.ws_b = slice + (size_t)p.splits * p.tiles * 32768;
     }
@@ -1039,79 +840,12 @@ extern "C" int vb_wgrad_bf16(void* stream, const vb_wgrad_bf16_args* a) {
     static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, HB_LDS);
     if (attr != hipSuccess) return (int)attr;
-    const int cus = hb_grid_limit();
-    const int grid = p.units < cus ? (p.units + 7) / 8 * 8 : cus;
-    hipLaunchKernelGGL(wgrad_bf16_kernel, dim3(grid), dim3(HB_THREADS), HB_LDS, st, p);
+    hipLaunchKernelGGL(wgrad_bf16_kernel, dim3(pl.grid), dim3(HB_THREADS), HB_LDS, st, p);
     VB_LAUNCH_CHECK();
     if (p.ws != nullptr && !(p.flags & 8)) {
         const long work = (long)p.tiles * 8192 + p.N;
         hipLaunchKernelGGL(wgrad_bf16_reduce_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, p);
         VB_LAUNCH_CHECK();
     }
-    return 0;
-}
-
-extern "C" int vb_cast_f32_bf16(void* stream, int64_t n, const float* x, uint16_t* y) {
-    if (x == nullptr || y == nullptr || n <= 0) return VB_E_BADARG;
-    if (!vb_aligned16(x) || !vb_aligned16(y)) return VB_E_ALIGN;
-    const long n8 = n / 8;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((n8 + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       n8, x, y, (long)n);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vb_cast_rows_f32_bf16(void* stream, int64_t rows, int32_t n, const float* x, int64_t ldx, uint16_t* y, int64_t ldy) {
-    if (x == nullptr || y == nullptr || rows <= 0 || n <= 0 || ldx < n || ldy < n) return VB_E_BADARG;
-    if (ldx % 4 != 0 || ldy % 8 != 0 || !vb_aligned16(x) || !vb_aligned16(y)) return VB_E_ALIGN;
-    const long work = rows * (ldy / 8);
-    hipLaunchKernelGGL(cast_rows_f32_bf16_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       (long)rows, (int)n, x, (long)ldx, y, (long)ldy);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vb_cast_bf16_f32(void* stream, int64_t n, const uint16_t* x, float* y) {
-    if (x == nullptr || y == nullptr || n <= 0) return VB_E_BADARG;
-    if (!vb_aligned16(x) || !vb_aligned16(y)) return VB_E_ALIGN;
-    const long n8 = n / 8;
-    hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3((unsigned)((n8 + 1 + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       n8, x, y, (long)n);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vb_weight_shadow_bf16(void* stream, int32_t rows, int32_t cols, const float* w, int64_t ldw, uint16_t* w16,
-                                     int64_t ld16, uint16_t* wt16, int64_t ldt) {
-    if (w == nullptr || (w16 == nullptr && wt16 == nullptr) || rows <= 0 || cols <= 0) return VB_E_BADARG;
-    if (rows % 64 != 0 || cols % 64 != 0 || ldw % 4 != 0 || !vb_aligned16(w)) return VB_E_ALIGN;
-    if (w16 != nullptr && (ld16 % 4 != 0 || ld16 < cols || (reinterpret_cast<uintptr_t>(w16) & 7u) != 0)) return VB_E_ALIGN;
-    if (wt16 != nullptr && (ldt % 4 != 0 || ldt < rows || (reinterpret_cast<uintptr_t>(wt16) & 7u) != 0)) return VB_E_ALIGN;
-    hipLaunchKernelGGL(weight_shadow_kernel, dim3(cols / 64, rows / 64), dim3(256), 0, static_cast<hipStream_t>(stream), rows, cols,
-                       w, (long)ldw, w16, (long)ld16, wt16, (long)ldt);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vb_weight_shadow_multi(void* stream, int32_t n_segs, const vb_shadow_seg* table, int64_t total_tiles) {
-    if (table == nullptr || n_segs <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffffL) return VB_E_BADARG;
-    hipLaunchKernelGGL(weight_shadow_multi_kernel, dim3((unsigned)total_tiles), dim3(256), 0, static_cast<hipStream_t>(stream), n_segs,
-                       table);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int64_t vb_colsum_bf16_workspace(int32_t cols) { return (int64_t)CS_SLABS * cols; }
-
-extern "C" int vb_colsum_bf16(void* stream, int64_t rows, int32_t cols, const uint16_t* x, int64_t ldx, float* out,
-                              float* workspace) {
-    if (x == nullptr || out == nullptr || workspace == nullptr || rows <= 0 || cols <= 0) return VB_E_BADARG;
-    if (cols % 4 != 0 || ldx % 4 != 0 || ldx < cols || (reinterpret_cast<uintptr_t>(x) & 7u) != 0 || !vb_aligned16(workspace))
-        return VB_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(colsum16_kernel, dim3((cols + 255) / 256, CS_SLABS), dim3(256), 0, st, (long)rows, cols, x, (long)ldx, workspace);
-    VB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(colsum16_finish_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, cols, workspace, out);
-    VB_LAUNCH_CHECK();
     return 0;
 }

@@ -1,5 +1,5 @@
 // Device-side pieces shared by the fp32 GEMM kernels (gemm.hip, gemm_planes.hip, gemm_v2.hip): LDS geometry of the
-// round-1 tiles, XCD-aware block map, the fused epilogues, operand staging, and the launchers each translation unit
+// round-1 tiles, XCD-aware block map (the persistent kernels' map: persistent_map.h), the fused epilogues, operand staging, and the launchers each translation unit
 // offers the others. The launch parameters (GemmP, EPI_*) and every planner live in gemm_plan.h (host-only).
 #pragma once
 #include "common.h"

@@ -21,6 +21,7 @@
 // on gemm_v2.h). Requires K % 32 == 0 (an even number of K steps per tile keeps the fragment-set parity static).
 #pragma once
 #include "gemm_v2.h"
+#include "persistent_map.h"
 
 namespace vbgemm {
 
@@ -55,47 +56,12 @@ struct V4Cfg {
     static_assert(LDS_BYTES <= 160 * 1024, "ring does not fit the CU");
 };
 
-// tile of block `b` in round `it` of a persistent launch over `tiles` output tiles on `grid` blocks: the blocks of one
-// XCD (b % 8) work on a contiguous run of tiles (N fastest) at any time, so they share A / W panels in their L2
-__device__ __forceinline__ int v4_tile_of(int b, int it, int grid, int tiles) {
-    const int base = it * grid;
-    const int n = min(grid, tiles - base);          // tiles of this round
-    if ((n & 7) != 0) return b < n ? base + b : -1;
-    const int per = n >> 3, x = b & 7, j = b >> 3;
-    return j < per ? base + x * per + j : -1;
-}
-
-// one LDS-DMA, lean form for the loader's inner loop: LDS[lds + 16 lane] <- *(base + off[lane]). The source address is
-// a wave-uniform 64-bit base (SGPR pair, advanced once per K step) plus a per-lane 32-bit byte offset that is constant
-// for a whole output tile, so a K step costs the loader 3 instructions per DMA and no vector ALU work at all. (The
-// first version bumped a 64-bit pointer per lane per DMA and saved / restored M0 around each one: 3,658 cycles per K step
-// to issue 24 DMAs - more than the 3,456 matrix-pipe cycles of the step, measured with the lab's loader counters.)
-// M0 is not preserved: nothing else in the loader wave uses it.
-__device__ __forceinline__ void v4_glds16(unsigned off, const float* base, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
-}
-
-// (row, column) of output tile `t`. The 32 tiles an XCD works on at any time (v4_tile_of) should share as few A / W
-// panels as possible: where the tile grid allows it they form a 4 x 8 patch (4 A panels + 8 W panels per XCD and round
-// instead of 1.3 + 24 for a 24-column grid walked row by row: measured 7.0x -> see profiles/r03_gemm_pmc.txt for
-// the operand bytes fetched through the fabric per launch); other grids are walked row by row (N fastest).
-__device__ __forceinline__ void v4_tile_rc(int t, int tiles, int tiles_n, int& r, int& c) {
-    const int tiles_m = tiles / tiles_n;
-    if ((tiles_n & 7) == 0 && (tiles_m & 3) == 0) {
-        const int patch = t >> 5, w = t & 31, pcols = tiles_n >> 3;
-        r = (patch / pcols) * 4 + (w >> 3);
-        c = (patch % pcols) * 8 + (w & 7);
-    } else {
-        r = t / tiles_n;
-        c = t % tiles_n;
-    }
-}
-
 // first row / column of the output tile block `b` works on in round `it`; false = no tile (the block is done).
 // MIXED (two tile heights in one launch; p.n_small = number of TALL row tiles, p.m_split = the rows they cover, 32 row tiles
 // in all, tiles_n a multiple of 8): block b = XCD x (b & 7), slot j (b >> 3); the XCD owns row tiles 4x .. 4x + 3, the slot
 // picks one of them (j >> 3) and a column (j & 7) inside the round's group of 8 columns - so a block keeps its row tile (and
-// with it its height class and its A panel) across the rounds, and an XCD works on a 4 x 8 patch as in the uniform map.
+// with it its height class and its A panel) across the rounds, and an XCD works on a 4 x 8 patch as in the uniform map
+// (persistent_map.h: tile_of / tile_rc).
 // BM is the CALLER's tile height: tall blocks only ever see tall row tiles, short blocks short ones.
 template <int BM, int BN, bool MIXED>
 __device__ __forceinline__ bool v4_origin(const GemmP& p, int b, int it, int grid, int tiles, int& m0, int& n0) {
@@ -107,10 +73,10 @@ __device__ __forceinline__ bool v4_origin(const GemmP& p, int b, int it, int gri
         n0 = c * BN;
         return true;
     }
-    const int t = v4_tile_of(b, it, grid, tiles);
+    const int t = tile_of(b, it, grid, tiles);
     if (t < 0) return false;
     int tr, tc;
-    v4_tile_rc(t, tiles, p.tiles_n, tr, tc);
+    tile_rc(t, tiles, p.tiles_n, tr, tc);
     m0 = tr * BM;
     n0 = tc * BN;
     return true;
@@ -167,11 +133,11 @@ __device__ __forceinline__ void v4_loader(const GemmP& p, const unsigned lds0, c
         const unsigned la = lds0 + (unsigned)stage_w * (Cfg::STAGE * 4);
         const unsigned lb = la + Cfg::A_SZ * 4;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) v4_glds16(oa[i], abase, la + 1024u * i);
+        for (int i = 0; i < NA; ++i) glds16(oa[i], abase, la + 1024u * i);
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
-            if (B_KC) v4_glds16(ob[i], bbase, lb + 1024u * i);
-            else if (okb[i]) v4_glds16(ob[i], bbase, lb + 1024u * i);
+            if (B_KC) glds16(ob[i], bbase, lb + 1024u * i);
+            else if (okb[i]) glds16(ob[i], bbase, lb + 1024u * i);
         }
         abase += V2_BK;
         if (B_KC) {
@@ -242,7 +208,7 @@ __device__ __forceinline__ void gemm_block_v4(const GemmP& p, float* __restrict_
     // rounds this block takes part in (a block whose tile index falls off the end of the last round stops earlier)
     int rounds = 0;
     if (MIXED) rounds = p.tiles_n >> 3;
-    else while (rounds * grid < tiles && v4_tile_of(b, rounds, grid, tiles) >= 0) ++rounds;
+    else while (rounds * grid < tiles && tile_of(b, rounds, grid, tiles) >= 0) ++rounds;
     if (rounds == 0) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef VB_GEMM_LAB

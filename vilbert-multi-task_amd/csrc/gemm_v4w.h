@@ -67,16 +67,16 @@ __device__ __forceinline__ void v4w_loader(const GemmP& p, const unsigned lds0, 
         const unsigned la = lds0 + (unsigned)stage_w * (Cfg::STAGE * 4);
         const unsigned lb = la + Cfg::A_SZ * 4;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) v4_glds16(oa[i], abase, la + 1024u * i);
+        for (int i = 0; i < NA; ++i) glds16(oa[i], abase, la + 1024u * i);
 #pragma unroll
-        for (int i = 0; i < NB; ++i) v4_glds16(ob[i], bbase, lb + 1024u * i);
+        for (int i = 0; i < NB; ++i) glds16(ob[i], bbase, lb + 1024u * i);
         abase += (long)V2_BK * p.lda;
         bbase += (long)V2_BK * p.ldb;
         stage_w = stage_w == S - 1 ? 0 : stage_w + 1;
         if (++kt == nk) {
             kt = 0;
             ++it;
-            if (it < rounds) set_unit(v4_tile_of(b, it, gridDim.x, units));
+            if (it < rounds) set_unit(tile_of(b, it, gridDim.x, units));
         }
     };
     auto wait_pending = [&](int k_tiles) {
@@ -85,7 +85,7 @@ __device__ __forceinline__ void v4w_loader(const GemmP& p, const unsigned lds0, 
         else v4_wait_vm<0>();
     };
     const int total = rounds * nk;
-    set_unit(v4_tile_of(b, 0, gridDim.x, units));
+    set_unit(tile_of(b, 0, gridDim.x, units));
     __builtin_amdgcn_s_setprio(2);
     for (int s = 0; s < S && s < total; ++s) issue_next();
     wait_pending(min(total, S) - 2);
@@ -107,7 +107,7 @@ __device__ __forceinline__ void gemm_block_v4w(const GemmP& p, float* __restrict
     const int nk = p.ktiles_per_split;       // even, the same for every unit
     const int b = blockIdx.x, grid = gridDim.x;
     int rounds = 0;
-    while (rounds * grid < units && v4_tile_of(b, rounds, grid, units) >= 0) ++rounds;
+    while (rounds * grid < units && tile_of(b, rounds, grid, units) >= 0) ++rounds;
     if (rounds == 0) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave == Cfg::MFMA_WAVES) {
@@ -179,7 +179,7 @@ __device__ __forceinline__ void gemm_block_v4w(const GemmP& p, float* __restrict
 
     __builtin_amdgcn_s_barrier();   // P0
     for (int it = 0; it < rounds; ++it) {
-        const int u = v4_tile_of(b, it, grid, units);
+        const int u = tile_of(b, it, grid, units);
         const int split = u / tiles, t = u - split * tiles;
         const int m0 = (t / p.tiles_n) * BM, n0 = (t % p.tiles_n) * BN;
         want_colsum = n0 == 0 && p.colsum[0] != nullptr && threadIdx.x < BM;

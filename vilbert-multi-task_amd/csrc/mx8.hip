@@ -42,6 +42,7 @@
 //             store, and a 32-column MX block is 16 in-lane values + ONE cross-lane exchange (lane ^ 32).
 #include "gemm_core.h"
 #include "mx8.h"
+#include "persistent_map.h"
 #include <type_traits>
 
 namespace {
@@ -119,38 +120,15 @@ struct MxP {
                  // 8 = no global stores in the epilogue, 16 = no epilogue at all
 };
 
-// tile of block `b` in round `it` (gemm_v4.h: v4_tile_of / v4_tile_rc): the 32 blocks of an XCD (b % 8) work on a 4 x 8
-// patch of tiles where the tile grid allows it, so they share A / W panels in their L2
-__device__ __forceinline__ int mx_tile_of(int b, int it, int grid, int tiles) {
-    const int base = it * grid;
-    const int n = min(grid, tiles - base);
-    if (n <= 0) return -1;
-    if ((n & 7) != 0) return b < n ? base + b : -1;
-    const int per = n >> 3, x = b & 7, j = b >> 3;
-    return j < per ? base + x * per + j : -1;
-}
-
+// first row / column of the output tile block `b` works on in round `it` (persistent_map.h); false = none
 __device__ __forceinline__ bool mx_origin(const MxP& p, int b, int it, int grid, int& m0, int& n0) {
-    const int t = mx_tile_of(b, it, grid, p.tiles);
+    const int t = tile_of(b, it, grid, p.tiles);
     if (t < 0) return false;
-    const int tiles_m = p.tiles / p.tiles_n;
     int r, c;
-    if ((p.tiles_n & 7) == 0 && (tiles_m & 3) == 0) {
-        const int patch = t >> 5, w = t & 31, pcols = p.tiles_n >> 3;
-        r = (patch / pcols) * 4 + (w >> 3);
-        c = (patch % pcols) * 8 + (w & 7);
-    } else {
-        r = t / p.tiles_n;
-        c = t % p.tiles_n;
-    }
+    tile_rc(t, p.tiles, p.tiles_n, r, c);
     m0 = r * MX_BM;
     n0 = c * MX_BN;
     return true;
-}
-
-// one LDS-DMA: LDS[lds + 16 lane] <- *(base + off[lane]), wave-uniform 64-bit base + per-lane 32-bit byte offset
-__device__ __forceinline__ void mx_glds16(unsigned off, const void* base, unsigned lds) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(base), "s"(lds) : "memory");
 }
 
 template <int N>
@@ -203,8 +181,8 @@ __device__ __forceinline__ void mx_loader(const MxP& p, const unsigned lds0, con
 #endif
         {
 #pragma unroll
-            for (int i = 0; i < ND; ++i) mx_glds16(off[i], base, l + REG + 1024u * i);
-            mx_glds16(soff, sbase, l + SREG);
+            for (int i = 0; i < ND; ++i) glds16(off[i], base, l + REG + 1024u * i);
+            glds16(soff, sbase, l + SREG);
         }
         base += MX_BK;
         sbase += sc_rows;
@@ -254,7 +232,7 @@ __global__ __launch_bounds__(MX_THREADS) void gemm_mx_kernel(const MxP p) {
     const int nk = p.K / MX_BK;
     const int b = blockIdx.x, grid = gridDim.x;
     int rounds = 0;
-    while (rounds * grid < p.tiles && mx_tile_of(b, rounds, grid, p.tiles) >= 0) ++rounds;
+    while (rounds * grid < p.tiles && tile_of(b, rounds, grid, p.tiles) >= 0) ++rounds;
     if (rounds == 0) return;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wave >= MX_MFMA_WAVES) {
