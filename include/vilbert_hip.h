@@ -776,6 +776,20 @@ typedef struct {
     const void* dy;                            /* backward: [M, H] */
     void* d_sum2; void* d_sum2_drop; void* d_pre; void* d_a1; void* d_sum1; void* d_sum1_drop; void* d_ctx;
     float* ln_ws;                              /* vb_layernorm_bwd(_bf16)_workspace(M, H) floats */
+    /* Optional row map (fp32 only; NULL = the block runs on every row, as above). With a map the forward and the
+     * input-gradient chain of the block run on M COMPACT rows: compact row r stands for row row_map[r] of the full
+     * [src_rows, .] tensors ctx and x, -1 = padding row (zeros in, nothing written back); a full row is named at most once.
+     * The dropout masks are those of the full tensor (indexed by the source row). sum1 ... y, dy and the d_* buffers have M
+     * rows. Every reduction over rows (weight, bias and LayerNorm gradients) runs at full size on zero-expanded operands in
+     * full_ws, in the order of the unmapped block: those gradients are bit for bit the ones of the block on every row with
+     * zero dy at the rows the map does not name. Backward also writes the full-size gradients the attention block reads
+     * (mapped rows: their values, all others 0; every row written once). ln_ws: sized for src_rows rows. */
+    const int32_t* row_map;                    /* [M] device */
+    int64_t src_rows;
+    void* ctx_rows;                            /* [M, Hc] the gathered context rows (forward scratch) */
+    void* d_ctx_full;                          /* backward: [src_rows, Hc] */
+    void* d_sum1_full;                         /* backward: [src_rows, H] */
+    float* full_ws;                            /* backward scratch: src_rows * (8 H + 2 I + 5) floats, 16-byte aligned */
 } vb_ffn_block;
 
 typedef struct {

@@ -5,6 +5,7 @@
 // disappears is the Python between them (argument structs, tensor allocation, autograd bookkeeping per op): ~55 ops per
 // connection layer and pass became one.
 #include "common.h"
+#include "row_map.h"
 #include <mutex>
 #include <unordered_map>
 
@@ -298,9 +299,76 @@ int attn_block_fwd(void* st, const vb_attn_block& b) {
     return attn_fwd<B16>(st, cross_call(b, B16, 2));
 }
 
+// ---- output + FFN block on a subset of its rows (vb_ffn_block.row_map; fp32) ------------------------------------------------
+// The GEMMs and LayerNorms run on the M compact rows as plain launches; what they cannot do with a map - read the context and
+// the residual at the source rows, draw the dropout mask of the FULL tensor - is done by the row kernels of rowmap.hip.
+int ffn_block_rows_fwd(void* st, const vb_ffn_block& f, bool training) {
+    hipStream_t hs = static_cast<hipStream_t>(st);
+    const long M = f.M, R = f.src_rows;
+    float *sum1 = static_cast<float*>(f.sum1), *sum2 = static_cast<float*>(f.sum2);
+    VB_TRY(vbrows::gather(hs, M, f.Hc, static_cast<const float*>(f.ctx), f.row_map, R, static_cast<float*>(f.ctx_rows)));
+    VB_TRY(linear<kF32>(st, M, f.o, f.ctx_rows, sum1, VB_ACT_NONE, nullptr, 0.f, 0, nullptr));
+    VB_TRY(vbrows::drop_add(hs, M, f.H, sum1, static_cast<const float*>(f.x), true, f.row_map, R, sum1, f.p_o, f.seed_o));
+    VB_TRY(ln_fwd<kF32>(st, M, f.H, sum1, f.ln1, f.eps, f.a1, training ? f.mean1 : nullptr, training ? f.rstd1 : nullptr));
+    VB_TRY(linear<kF32>(st, M, f.f1, f.a1, f.h, VB_ACT_GELU, nullptr, 0.f, 0, training ? f.dact : nullptr));
+    VB_TRY(linear<kF32>(st, M, f.f2, f.h, sum2, VB_ACT_NONE, nullptr, 0.f, 0, nullptr));
+    VB_TRY(vbrows::drop_add(hs, M, f.H, sum2, static_cast<const float*>(f.a1), false, f.row_map, R, sum2, f.p_f, f.seed_f));
+    return ln_fwd<kF32>(st, M, f.H, sum2, f.ln2, f.eps, f.y, training ? f.mean2 : nullptr, training ? f.rstd2 : nullptr);
+}
+
+// Backward: the input-gradient chain (three GEMMs) runs on the compact rows; every reduction over rows - the three weight /
+// bias gradients, the LayerNorm parameter gradients - runs at FULL size, on operands expanded with zero rows into full_ws,
+// by the launches of the unmapped block: a zero dy row adds exact zeros, so these gradients are those of the block on every
+// row bit for bit (a compact reduction would add the same terms in another grouping). The LayerNorm backward at full size
+// also yields d_sum1 as the attention block reads it and the dropped twins with the masks of the full tensor.
+int ffn_block_rows_bwd(void* st, WgradQueue& wq, const vb_ffn_block& f) {
+    hipStream_t hs = static_cast<hipStream_t>(st);
+    const long M = f.M, R = f.src_rows;
+    const vbrows::FullWs w(R, f.H, f.I);
+    float* ws = f.full_ws;
+    int32_t* inv = reinterpret_cast<int32_t*>(ws + w.inv);
+    float* stats = ws + w.stats;
+    auto compact = [](const void* p) { return static_cast<const float*>(p); };
+    VB_TRY(vbrows::invert(hs, R, M, f.row_map, inv));
+    VB_TRY(vbrows::scatter_stats(hs, R, f.mean1, f.rstd1, f.mean2, f.rstd2, inv, stats));
+    // y = LN(sum2)
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.dy), inv, ws + w.dy));
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.sum2), inv, ws + w.sum2));
+    VB_TRY(ln_bwd<kF32>(st, R, f.H, ws + w.dy, ws + w.sum2, stats + 2 * R, stats + 3 * R, f.ln2, ws + w.d_sum2, f.ln_ws,
+                        ws + w.d_sum2_drop, f.p_f, f.seed_f));
+    const float* dyd_full = f.p_f > 0.f ? ws + w.d_sum2_drop : ws + w.d_sum2;
+    VB_TRY(vbrows::gather(hs, M, f.H, ws + w.d_sum2, f.row_map, R, static_cast<float*>(f.d_sum2)));
+    const void* dyd = f.d_sum2;
+    if (f.p_f > 0.f) {
+        VB_TRY(vbrows::gather(hs, M, f.H, dyd_full, f.row_map, R, static_cast<float*>(f.d_sum2_drop)));
+        dyd = f.d_sum2_drop;
+    }
+    // sum2 = dropout(h W2^T + b2) + a1;  h = gelu(pre)
+    VB_TRY(dgrad<kF32>(st, M, f.f2, dyd, f.d_pre, nullptr, f.dact));
+    VB_TRY(vbrows::scatter(hs, R, f.I, compact(f.h), inv, ws + w.h));
+    wq.push(R, f.f2, dyd_full, ws + w.h);
+    VB_TRY(dgrad<kF32>(st, M, f.f1, f.d_pre, f.d_a1, f.d_sum2, nullptr));
+    VB_TRY(vbrows::scatter(hs, R, f.I, compact(f.d_pre), inv, ws + w.d_pre));
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.a1), inv, ws + w.a1));
+    wq.push(R, f.f1, ws + w.d_pre, ws + w.a1);
+    // a1 = LN(sum1): d_sum1 at full size is what the attention block reads
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.d_a1), inv, ws + w.d_a1));
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.sum1), inv, ws + w.sum1));
+    VB_TRY(ln_bwd<kF32>(st, R, f.H, ws + w.d_a1, ws + w.sum1, stats, stats + R, f.ln1, f.d_sum1_full, f.ln_ws,
+                        ws + w.d_sum1_drop, f.p_o, f.seed_o));
+    const float* dod_full = f.p_o > 0.f ? ws + w.d_sum1_drop : static_cast<const float*>(f.d_sum1_full);
+    float* dod = static_cast<float*>(f.p_o > 0.f ? f.d_sum1_drop : f.d_sum1);
+    VB_TRY(vbrows::gather(hs, M, f.H, dod_full, f.row_map, R, dod));
+    // sum1 = dropout(ctx Wo^T + bo) + x
+    VB_TRY(dgrad<kF32>(st, M, f.o, dod, f.d_ctx, nullptr, nullptr));
+    wq.push(R, f.o, dod_full, f.ctx);
+    return vbrows::scatter(hs, R, f.Hc, compact(f.d_ctx), inv, static_cast<float*>(f.d_ctx_full));
+}
+
 template <bool B16>
 int ffn_block_fwd(void* st, const vb_ffn_block& f, bool training) {
     if (f.M == 0) return 0;
+    if (f.row_map != nullptr) return ffn_block_rows_fwd(st, f, training);
     VB_TRY(linear<B16>(st, f.M, f.o, f.ctx, f.sum1, VB_ACT_NONE, f.x, f.p_o, f.seed_o, nullptr));
     VB_TRY(ln_fwd<B16>(st, f.M, f.H, f.sum1, f.ln1, f.eps, f.a1, training ? f.mean1 : nullptr, training ? f.rstd1 : nullptr));
     VB_TRY(linear<B16>(st, f.M, f.f1, f.a1, f.h, VB_ACT_GELU, nullptr, 0.f, 0, training ? f.dact : nullptr));
@@ -311,6 +379,7 @@ int ffn_block_fwd(void* st, const vb_ffn_block& f, bool training) {
 template <bool B16>
 int ffn_block_bwd(void* st, WgradQueue& wq, const vb_ffn_block& f) {
     if (f.M == 0) return 0;
+    if (f.row_map != nullptr) return ffn_block_rows_bwd(st, wq, f);
     // y = LN(sum2)
     VB_TRY(ln_bwd<B16>(st, f.M, f.H, f.dy, f.sum2, f.mean2, f.rstd2, f.ln2, f.d_sum2, f.ln_ws, f.d_sum2_drop, f.p_f, f.seed_f));
     const void* dyd = f.p_f > 0.f ? f.d_sum2_drop : f.d_sum2;
@@ -393,6 +462,7 @@ int check(const vb_layer_args* a, bool backward) {
                 return VB_E_BADARG;
             if ((f->p_f > 0.f && f->d_sum2_drop == nullptr) || (f->p_o > 0.f && f->d_sum1_drop == nullptr)) return VB_E_BADARG;
         }
+        if (int e = vbrows::check_row_map(*f, b16, backward)) return e;
     }
     if (backward && has_attn &&
         (b.dqkv1 == nullptr || b.dvec == nullptr || b.d_ctx1 == nullptr || b.lse1 == nullptr ||

@@ -1,0 +1,142 @@
+// Row kernels of an output + feed-forward block that runs on a SUBSET of its rows (vb_ffn_block.row_map; layers.hip):
+//   gather        out[r] = src[map[r]]                                    (padding rows, map[r] = -1: zeros)
+//   drop + add    out[r] = dropout(lin[r]) + res[map[r] or r]             (the dropout / residual epilogue of the GEMMs, with
+//                                                                          the mask of the FULL tensor: keep(seed, map[r] N + col))
+//   invert        inv[R] = the r with map[r] == R, or -1
+//   scatter       full[R] = compact[inv[R]]                               (rows no compact row stands for: zeros)
+// fp32, 16-byte accesses (cols % 4 == 0). The GEMM and LayerNorm kernels themselves know nothing of the map.
+#include "common.h"
+#include "rng.h"
+#include "row_map.h"
+
+namespace {
+
+__device__ __forceinline__ long source_row(const int32_t* __restrict__ map, long r, long src_rows) {
+    const long s = map[r];
+    return s >= 0 && s < src_rows ? s : -1;        // (anything outside the full tensor is a padding row)
+}
+
+__global__ __launch_bounds__(256) void gather_rows_kernel(long M, int cols4, const f32x4* __restrict__ src,
+                                                          const int32_t* __restrict__ map, long src_rows,
+                                                          f32x4* __restrict__ out) {
+    const long n = M * cols4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cols4, c = i - r * cols4;
+        const long s = source_row(map, r, src_rows);
+        out[i] = s >= 0 ? src[s * cols4 + c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// lin and out may be the same buffer (every element is read and written by the same thread)
+__global__ __launch_bounds__(256) void row_drop_add_kernel(long M, int cols4, const f32x4* lin, const f32x4* __restrict__ res,
+                                                           int res_mapped, const int32_t* __restrict__ map, long src_rows,
+                                                           f32x4* out, float p, float scale, uint64_t seed_in,
+                                                           const uint64_t* __restrict__ epoch) {
+    const uint64_t seed = p > 0.f ? vb_seed_with_epoch(seed_in, epoch) : 0;
+    const long n = M * cols4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long r = i / cols4, c = i - r * cols4;
+        const long s = source_row(map, r, src_rows);
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (s >= 0) {
+            f32x4 v = lin[i];
+            if (p > 0.f) {
+                const uint64_t idx = (uint64_t)((s * cols4 + c) * 4);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = vb_keep(seed, idx + e, p) ? v[e] * scale : 0.f;
+            }
+            o = v;
+            if (res != nullptr) o += res[(res_mapped ? s : r) * cols4 + c];
+        }
+        out[i] = o;
+    }
+}
+
+// inv[R] = the compact row that stands for full row R, or -1: one wave per full row scans the map, 64 entries per step, and
+// takes the first entry that names R - every inv[R] written exactly once, no pass that clears it first, no atomics
+__global__ __launch_bounds__(256) void invert_map_kernel(long src_rows, int M, const int32_t* __restrict__ map,
+                                                         int32_t* __restrict__ inv) {
+    const int lane = threadIdx.x & 63;
+    const long R = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (R >= src_rows) return;
+    int found = -1;
+    for (int base = 0; base < M && found < 0; base += 64) {
+        const int r = base + lane;
+        const unsigned long long hits = __ballot(r < M && (long)map[r] == R);
+        if (hits != 0) found = base + __ffsll(hits) - 1;
+    }
+    if (lane == 0) inv[R] = found;
+}
+
+// full[R] = compact[inv[R]], zeros where no compact row stands for R
+__global__ __launch_bounds__(256) void scatter_rows_kernel(long src_rows, int cols4, const f32x4* __restrict__ compact,
+                                                           const int32_t* __restrict__ inv, f32x4* __restrict__ full) {
+    const long n = src_rows * cols4;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const long R = i / cols4, c = i - R * cols4;
+        const long r = inv[R];
+        full[i] = r >= 0 ? compact[r * cols4 + c] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
+// the same for four per-row scalars (LayerNorm statistics): full[k][R] = v_k[inv[R]] or 0
+__global__ __launch_bounds__(256) void scatter_stats_kernel(long src_rows, const float* __restrict__ v0, const float* __restrict__ v1,
+                                                            const float* __restrict__ v2, const float* __restrict__ v3,
+                                                            const int32_t* __restrict__ inv, float* __restrict__ full) {
+    for (long R = (long)blockIdx.x * blockDim.x + threadIdx.x; R < src_rows; R += (long)gridDim.x * blockDim.x) {
+        const long r = inv[R];
+        full[R] = r >= 0 ? v0[r] : 0.f;
+        full[src_rows + R] = r >= 0 ? v1[r] : 0.f;
+        full[2 * src_rows + R] = r >= 0 ? v2[r] : 0.f;
+        full[3 * src_rows + R] = r >= 0 ? v3[r] : 0.f;
+    }
+}
+
+inline unsigned grid_for(long work_items) {
+    long blocks = (work_items + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
+}
+
+}  // namespace
+
+namespace vbrows {
+
+int gather(hipStream_t st, long M, int cols, const float* src, const int32_t* map, long src_rows, float* out) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(M * (cols / 4))), dim3(256), 0, st, M, cols / 4,
+                       reinterpret_cast<const f32x4*>(src), map, src_rows, reinterpret_cast<f32x4*>(out));
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+int drop_add(hipStream_t st, long M, int cols, const float* lin, const float* res, bool res_mapped, const int32_t* map,
+             long src_rows, float* out, float p, uint64_t seed) {
+    hipLaunchKernelGGL(row_drop_add_kernel, dim3(grid_for(M * (cols / 4))), dim3(256), 0, st, M, cols / 4,
+                       reinterpret_cast<const f32x4*>(lin), reinterpret_cast<const f32x4*>(res), res_mapped ? 1 : 0, map, src_rows,
+                       reinterpret_cast<f32x4*>(out), p, 1.0f / (1.0f - p), seed, p > 0.f ? vb_seed_epoch() : nullptr);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+int invert(hipStream_t st, long src_rows, long M, const int32_t* map, int32_t* inv) {
+    hipLaunchKernelGGL(invert_map_kernel, dim3((unsigned)((src_rows + 3) / 4)), dim3(256), 0, st, src_rows, (int)M, map, inv);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+int scatter(hipStream_t st, long src_rows, int cols, const float* compact, const int32_t* inv, float* full) {
+    hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(src_rows * (cols / 4))), dim3(256), 0, st, src_rows, cols / 4,
+                       reinterpret_cast<const f32x4*>(compact), inv, reinterpret_cast<f32x4*>(full));
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+int scatter_stats(hipStream_t st, long src_rows, const float* v0, const float* v1, const float* v2, const float* v3,
+                  const int32_t* inv, float* full) {
+    hipLaunchKernelGGL(scatter_stats_kernel, dim3(grid_for(src_rows)), dim3(256), 0, st, src_rows, v0, v1, v2, v3, inv, full);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace vbrows

@@ -143,6 +143,8 @@ class FfnBlock(ctypes.Structure):
         ("d_sum2", ctypes.c_void_p), ("d_sum2_drop", ctypes.c_void_p), ("d_pre", ctypes.c_void_p), ("d_a1", ctypes.c_void_p),
         ("d_sum1", ctypes.c_void_p), ("d_sum1_drop", ctypes.c_void_p), ("d_ctx", ctypes.c_void_p),
         ("ln_ws", _c_f32p),
+        ("row_map", ctypes.c_void_p), ("src_rows", ctypes.c_int64), ("ctx_rows", ctypes.c_void_p),
+        ("d_ctx_full", ctypes.c_void_p), ("d_sum1_full", ctypes.c_void_p), ("full_ws", _c_f32p),
     ]
 
 

@@ -171,7 +171,7 @@ def _call(fn, a, what):
 # Plans: the static half of a node
 # ---------------------------------------------------------------------------------------------------------------------
 class _Plan(object):
-    __slots__ = ("params", "ptrs", "b16", "training", "tmpl", "c_fwd", "c_bwd", "dims")
+    __slots__ = ("params", "ptrs", "b16", "training", "tmpl", "c_fwd", "c_bwd", "dims", "row_cap")
 
     def new_args(self):
         return N.LayerArgs.from_buffer_copy(self.tmpl)
@@ -357,29 +357,40 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def _self_plan(p, adims, dims, b16, training):
+def _self_plan(p, adims, dims, b16, training, row_cap=None):
+    """row_cap: the output + FFN block runs on a row map of at most that many compact rows (vb_ffn_block.row_map): its buffers
+    are laid out for row_cap rows, the attention block's (and the two full-size gradients the block hands to it) for all."""
     plan = _Plan()
     plan.params, plan.b16, plan.training = list(p), b16, training
-    plan.dims = (adims, dims)
+    plan.dims, plan.row_cap = (adims, dims), row_cap
     B, heads, _d, S, _n2 = adims
     M, _Hc, H, I, _eps = dims
+    Mb = M if row_cap is None else row_cap
     es = 2 if b16 else 4
     c = plan.c_fwd = _Carver()
-    _ffn_sizes(c, M, H, I, es, training)
+    _ffn_sizes(c, Mb, H, I, es, training)
     c.add("qkv", M * 3 * H * es)
     c.add("ctx", M * H * es)
+    if row_cap is not None:
+        c.add("ctx_rows", Mb * H * es)
     if training:
         c.add("lse", B * heads * S * 4)
     t = plan.c_bwd = _Carver()
-    _ffn_bwd_sizes(t, M, H, I, es)
+    _ffn_bwd_sizes(t, Mb, H, I, es)
     t.add("d_sum1", M * H * es)
     t.add("d_ctx", M * H * es)
+    if row_cap is not None:
+        t.add("d_sum1_rows", Mb * H * es)
+        t.add("d_ctx_rows", Mb * H * es)
+        t.add("full_ws", M * (8 * H + 2 * I + 5) * 4)       # (vb_ffn_block.full_ws: operands of the full-size reductions)
     t.add("dqkv", M * 3 * H * es)
     t.add("dvec", B * heads * S * 4)
     a = N.LayerArgs()
     a.dtype, a.training = (1 if b16 else 0), int(training)
     _static_attn(a.attn, adims, p)
     _static_ffn(a.s1, p[6:], dims)
+    if row_cap is not None:
+        a.s1.src_rows = M
     _seal(plan, a)
     return plan
 
@@ -387,32 +398,38 @@ def _self_plan(p, adims, dims, b16, training):
 class SelfLayerFn(Function):
     """A whole BertLayer / BertImageLayer: q|k|v projection, attention, output projection + LayerNorm, feed-forward +
     LayerNorm. params: q.w q.b k.w k.b v.w v.b, then the ten of the output + FFN block.
-    dyn = (p_o, p_f, seed_o, seed_f, p1, seed1)"""
+    dyn = (p_o, p_f, seed_o, seed_f, p1, seed1)
+    rows: None, or the int32 row map of the output + FFN block (vb_ffn_block.row_map: compact row -> row of x, -1 = padding;
+    at most the plan's row_cap entries, a row of x at most once): y is then [len(rows), H] and the rows of x no entry names
+    get a zero gradient from the block - the attention part still runs on every row, and the parameter gradients are bit for
+    bit those of the whole layer with a zero dy at the other rows."""
 
     @staticmethod
-    def forward(ctx, x, mask, plan, dyn, *p):
+    def forward(ctx, x, mask, rows, plan, dyn, *p):
         b16, training, c = plan.b16, plan.training, plan.c_fwd
         (B, _heads, _d, S, _n2), _dims = plan.dims
         x = ops._contig(x)
         mask = _mask2d(mask, B, S)
         buf = c.alloc(x.device)
         base = buf.data_ptr()
-        y = torch.empty_like(x)
+        y = torch.empty_like(x) if rows is None else torch.empty((rows.numel(), x.shape[-1]), dtype=x.dtype, device=x.device)
         a = plan.new_args()
         cx = c.at(base, "ctx")
         _dyn_attn_fwd(a.attn, 0, x.data_ptr(), None, _ptr(mask), None, c.at(base, "qkv"), None, cx, None,
                       c.at(base, "lse") if training else None, None, p, (dyn[4], 0.0, dyn[5], 0), b16)
         _dyn_ffn_fwd(a.s1, c, base, cx, x.data_ptr(), y.data_ptr(), p[6:], dyn[:4], b16, training)
+        if rows is not None:
+            a.s1.M, a.s1.row_map, a.s1.ctx_rows = rows.numel(), rows.data_ptr(), c.at(base, "ctx_rows")
         _call(N.lib().vb_layer_fwd, a, "vb_layer_fwd")
         if training:
-            ctx.save_for_backward(x, mask, buf, *p)
+            ctx.save_for_backward(x, mask, buf, rows, *p)
             ctx.plan, ctx.dyn = plan, dyn
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, mask, buf = ctx.saved_tensors[:3]
-        p = ctx.saved_tensors[3:]
+        x, mask, buf, rows = ctx.saved_tensors[:4]
+        p = ctx.saved_tensors[4:]
         plan, dyn = ctx.plan, ctx.dyn
         b16, c, t = plan.b16, plan.c_fwd, plan.c_bwd
         _adims, (M, _Hc, H, _I, _eps) = plan.dims
@@ -430,7 +447,17 @@ class SelfLayerFn(Function):
         _dyn_attn_fwd(a.attn, 0, x.data_ptr(), None, _ptr(mask), None, c.at(base, "qkv"), None, cx, None, c.at(base, "lse"), None,
                       p, (dyn[4], 0.0, dyn[5], 0), b16)
         _dyn_ffn_fwd(a.s1, c, base, cx, x.data_ptr(), c.at(base, "sum1"), p[6:], dyn[:4], b16, True)
-        _dyn_ffn_bwd(a.s1, t, tbase, dy.data_ptr(), d_sum1, d_ctx, tg, 6, _ln_ws(dev, M, H, b16), dyn)
+        if rows is None:
+            _dyn_ffn_bwd(a.s1, t, tbase, dy.data_ptr(), d_sum1, d_ctx, tg, 6, _ln_ws(dev, M, H, b16), dyn)
+        else:
+            # the block's input-gradient chain is compact; its reductions over rows (weight / LayerNorm gradients) run at
+            # full size in full_ws, and it writes the full-size gradients the attention block reads
+            f = a.s1
+            _dyn_ffn_bwd(f, t, tbase, dy.data_ptr(), t.at(tbase, "d_sum1_rows"), t.at(tbase, "d_ctx_rows"), tg, 6,
+                         _ln_ws(dev, M, H, b16), dyn)
+            f.M, f.row_map, f.ctx_rows = rows.numel(), rows.data_ptr(), c.at(base, "ctx_rows")
+            f.d_sum1_full, f.d_ctx_full = d_sum1, d_ctx
+            f.full_ws = t.at(tbase, "full_ws")
         b = a.attn
         b.d_ctx1, b.dqkv1, b.dvec = d_ctx, t.at(tbase, "dqkv"), t.at(tbase, "dvec")
         b.dres1, b.dx1 = d_sum1, dx.data_ptr()
@@ -440,7 +467,7 @@ class SelfLayerFn(Function):
             for tt in (buf, tbuf, x):
                 tt.record_stream(ws_stream)
         grads = tg.finish()
-        return (dx, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None) + tuple(grads)
 
 
 def _bi_plan(p, adims, b16, training):
@@ -632,10 +659,20 @@ def _self_params(layer):
     return qkv + _block_params(layer.attention.output.dense, layer.attention.output.LayerNorm, layer.intermediate, layer.output)
 
 
-def self_layer(layer, x, mask, drop_attn, drop_o, drop_f):
+def rows_enabled():
+    """The last layers of a pre-training step may run their output + FFN block on the rows the losses read
+    (vilbert.BertForMultiModalPreTraining); `VB_LAST_LAYER_ROWS=0` keeps every row."""
+    return _STATE["on"] and os.environ.get("VB_LAST_LAYER_ROWS", "1") != "0"
+
+
+def self_layer(layer, x, mask, drop_attn, drop_o, drop_f, rows=None):
     """BertLayer / BertImageLayer forward on the native launcher, or None when the per-op path has to serve this call.
-    drop_*: the effective dropout probabilities of the three nn.Dropout children."""
+    drop_*: the effective dropout probabilities of the three nn.Dropout children. rows: SelfLayerFn's row map (fp32 training
+    only: any other call with a map is refused) - the result is then [len(rows), H]."""
     if not _STATE["on"] or x.dim() != 3 or not _dtype_ok(x):
+        return None
+    if rows is not None and (x.dtype == BF16 or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_contiguous()
+                             or rows.device != x.device):
         return None
     att = layer.attention.self
     if att.visualization or getattr(att, "dynamic_attention", False):
@@ -665,23 +702,30 @@ def self_layer(layer, x, mask, drop_attn, drop_o, drop_f):
     if state is None:
         return None
     training = state == "train"
-    plan = plans.get(training)
+    if rows is not None and (not training or H % 4 != 0 or layer.intermediate.dense.weight.shape[0] % 4 != 0):
+        return None
+    # a plan with a row map is kept per row CAPACITY (its buffers are laid out for that many rows; the number of rows of a
+    # call is a field of the call): the largest map seen so far serves every smaller one
+    pkey = training if rows is None else "rows"
+    plan = plans.get(pkey)
+    if plan is not None and rows is not None and plan.valid() and rows.numel() > plan.row_cap:
+        plan = None
     if plan is None or not plan.valid():
         if plan is not None:                 # moved parameters (model.to(), new storage): judge them again next call
             del cache[key]
-            return self_layer(layer, x, mask, drop_attn, drop_o, drop_f)
+            return self_layer(layer, x, mask, drop_attn, drop_o, drop_f, rows)
         adims = (B, att.num_attention_heads, att.attention_head_size, S, 0)
         dims = (B * S, H, H, layer.intermediate.dense.weight.shape[0], layer.output.LayerNorm.variance_epsilon)
-        plan = plans[training] = _self_plan(params, adims, dims, b16, training)
+        plan = plans[pkey] = _self_plan(params, adims, dims, b16, training, None if rows is None else rows.numel())
     # seeds in the order the per-op path draws them: attention, output projection, feed-forward
     seed1 = A.next_seed() if drop_attn > 0.0 else 0
     seed_o = A.next_seed() if drop_o > 0.0 else 0
     seed_f = A.next_seed() if drop_f > 0.0 else 0
     dyn = (drop_o, drop_f, seed_o, seed_f, drop_attn, seed1)
     if training:
-        return SelfLayerFn.apply(x, mask, plan, dyn, *params)
+        return SelfLayerFn.apply(x, mask, rows, plan, dyn, *params)
     with torch.no_grad():
-        return SelfLayerFn.forward(_NoCtx, x, mask, plan, dyn, *params)
+        return SelfLayerFn.forward(_NoCtx, x, mask, None, plan, dyn, *params)
 
 
 def _conn_params(layer):

@@ -345,6 +345,14 @@ class BertOutput(_ResidualNormOutput):
                                          config.hidden_dropout_prob)
 
 
+def _gather_rows(y, rows):
+    """[B, S, H] -> the [len(rows), H] rows a row map names (-1: a zero row). Only for a layer the native launcher refused
+    although it was asked for these rows only: the whole layer ran."""
+    idx = rows.to(torch.int64)
+    picked = y.reshape(-1, y.size(-1)).index_select(0, idx.clamp(min=0))
+    return picked * (idx >= 0).unsqueeze(1).to(picked.dtype)
+
+
 class BertLayer(nn.Module):
     """Reference vilbert.py:520-533."""
 
@@ -355,9 +363,15 @@ class BertLayer(nn.Module):
         self.output = BertOutput(config)
 
     def forward(self, hidden_states, attention_mask):
+        # `_rows` (internal, left on the module by BertEncoder for this one call - forward keeps the reference's signature):
+        # int32 row map, the caller reads the output at these rows only (-1: a padding row) and gets [len(rows), H]
+        rows = self.__dict__.pop("_rows", None)
         # one autograd node / one call across the C ABI for the whole layer (layers.py, csrc/layers.hip) ...
         y = layers.self_layer(self, hidden_states, attention_mask, _drop_p(self.attention.self.dropout),
-                              _drop_p(self.attention.output.dropout), _drop_p(self.output.dropout))
+                              _drop_p(self.attention.output.dropout), _drop_p(self.output.dropout), rows)
+        if y is None and rows is not None:      # (refused with a map: the whole layer, then its rows)
+            y, probs = self.forward(hidden_states, attention_mask)
+            return _gather_rows(y, rows), probs
         if y is not None:
             return y, None
         # ... or op by op (attention maps wanted, fp8 / MX inference, shapes the launcher does not take)
@@ -443,8 +457,12 @@ class BertImageLayer(nn.Module):
         self.output = BertImageOutput(config)
 
     def forward(self, hidden_states, attention_mask, txt_embedding, txt_attention_mask):
+        rows = self.__dict__.pop("_rows", None)          # (as BertLayer.forward)
         y = layers.self_layer(self, hidden_states, attention_mask, _drop_p(self.attention.self.dropout),
-                              _drop_p(self.attention.output.dropout), _drop_p(self.output.dropout))
+                              _drop_p(self.attention.output.dropout), _drop_p(self.output.dropout), rows)
+        if y is None and rows is not None:
+            y, probs = self.forward(hidden_states, attention_mask, txt_embedding, txt_attention_mask)
+            return _gather_rows(y, rows), probs
         if y is not None:
             return y, None
         attention_output, attention_probs = self.attention(hidden_states, attention_mask, txt_embedding,
@@ -585,9 +603,25 @@ class BertEncoder(nn.Module):
         self.v_layer = nn.ModuleList([copy.deepcopy(v_layer) for _ in range(config.v_num_hidden_layers)])
         self.c_layer = nn.ModuleList([copy.deepcopy(connect_layer) for _ in range(len(config.v_biattention_id))])
 
+    def tail_takes_rows(self):
+        """A text layer and an image layer follow the last connection layer (never frozen: fixed_*_layer <= every connection
+        point) and the batch keeps its size: forward can apply row maps (`_last_layer_rows`) to the last layer of each."""
+        t_last = self.t_biattention_id[-1] if len(self.t_biattention_id) else 0
+        v_last = self.v_biattention_id[-1] if len(self.v_biattention_id) else 0
+        dynamic = len(self.v_layer) > 0 and self.v_layer[0].attention.self.dynamic_attention
+        return len(self.layer) > t_last and len(self.v_layer) > v_last and not dynamic and not self.FAST_MODE \
+            and not self.in_batch_pairs
+
     def forward(self, txt_embedding, image_embedding, txt_attention_mask, txt_attention_mask2,
                 image_attention_mask, co_attention_mask=None, output_all_encoded_layers=True,
                 output_all_attention_masks=False):
+        # `_last_layer_rows` (internal, left on the module by BertForMultiModalPreTraining for this one call - forward keeps the
+        # reference's signature): (text row map, image row map) - the caller reads the final hidden states at these rows
+        # only, and the last text / image layer return [len(map), H] instead of [B, S, H]. Needs tail_takes_rows().
+        last_layer_rows = self.__dict__.pop("_last_layer_rows", None)
+        if last_layer_rows is not None:
+            assert self.tail_takes_rows() and not output_all_encoded_layers and not output_all_attention_masks
+        rows_t, rows_v = last_layer_rows if last_layer_rows is not None else (None, None)
         v_start = t_start = count = 0
         all_encoder_layers_t, all_encoder_layers_v = [], []
         all_attention_mask_t, all_attnetion_mask_v, all_attention_mask_c = [], [], []
@@ -603,16 +637,20 @@ class BertEncoder(nn.Module):
                 return F.to_f32(x)
             return x
 
-        def run_text(lo, hi, x, frozen=False):
+        def run_text(lo, hi, x, frozen=False, rows=None):
             for idx in range(lo, hi):
+                if rows is not None and idx == hi - 1:
+                    self.layer[idx].__dict__["_rows"] = rows
                 with torch.set_grad_enabled(torch.is_grad_enabled() and not frozen):
                     x, probs = self.layer[idx](x, txt_attention_mask)
                 if output_all_attention_masks:
                     all_attention_mask_t.append(probs)
             return thaw(x, frozen)
 
-        def run_image(lo, hi, x, frozen=False):
+        def run_image(lo, hi, x, frozen=False, rows=None):
             for idx in range(lo, hi):
+                if rows is not None and idx == hi - 1:
+                    self.v_layer[idx].__dict__["_rows"] = rows
                 with torch.set_grad_enabled(torch.is_grad_enabled() and not frozen):
                     x, probs = self.v_layer[idx](x, image_attention_mask, txt_embedding, txt_attention_mask2)
                 if output_all_attention_masks:
@@ -682,8 +720,9 @@ class BertEncoder(nn.Module):
 
         if len(self.v_layer) > v_start and len(self.layer) > t_start and not dynamic:
             image_embedding, txt_embedding = _concurrent(
-                lambda: run_image(v_start, len(self.v_layer), image_embedding),
-                lambda: run_text(t_start, len(self.layer), txt_embedding), [image_embedding, image_attention_mask],
+                lambda: run_image(v_start, len(self.v_layer), image_embedding, rows=rows_v),
+                lambda: run_text(t_start, len(self.layer), txt_embedding, rows=rows_t),
+                [image_embedding, image_attention_mask] + ([rows_v] if rows_v is not None else []),
                 enabled=not output_all_attention_masks)
         else:
             image_embedding = run_image(v_start, len(self.v_layer), image_embedding)
@@ -799,6 +838,30 @@ class BertImagePredictionHead(nn.Module):
 def _capacity(positions, frac):
     """Fixed gather capacity: `frac` of the positions, a multiple of 32 (aligned wgrad contraction, whole MFMA tiles)."""
     return max(32, min((positions + 31) // 32 * 32, (int(positions * frac) + 31) // 32 * 32))
+
+
+def _row_map(idx, n_valid, batch, per_sample):
+    """Row map of a last encoder layer (layers.SelfLayerFn) for a pre-training step: the rows of its [batch * per_sample, H]
+    output the poolers and a prediction head read -> (map int32, head index int64 [cap]).
+      entries 0 .. batch - 1:            row 0 of every sample (the poolers)
+      entries batch .. batch + cap - 1:  the labelled rows idx[0 : n_valid]; -1 (padding: a zero row, no gradient) behind them
+                                         and where the labelled row is a sample's row 0 - that row is in the map already
+      then -1 up to a multiple of 32 rows (aligned weight-gradient contraction, _capacity).
+    idx: int64 [cap] rows of the fixed-capacity gather (whatever its fill value behind n_valid), n_valid: device scalar. The
+    head reads the compact output at head index[i] for idx[i]: entry batch + i, or the pooler entry of that sample. Every
+    row is in the map ONCE, so each gets the gradient the whole layer's row would get: the sum of its readers' gradients."""
+    cap = idx.numel()
+    dev = idx.device
+    slot = torch.arange(cap, device=dev)
+    valid = slot < n_valid
+    pooled = valid & (idx % per_sample == 0)
+    labelled = torch.where(valid & ~pooled, idx, torch.full_like(idx, -1))
+    head = torch.where(pooled, torch.div(idx, per_sample, rounding_mode="floor"), slot + batch)
+    parts = [torch.arange(batch, device=dev, dtype=idx.dtype) * per_sample, labelled]
+    pad = -(batch + cap) % 32
+    if pad:
+        parts.append(torch.full((pad,), -1, dtype=idx.dtype, device=dev))
+    return torch.cat(parts).to(torch.int32), head
 
 
 def _fuse_pooled(fusion_method, pooled_output_t, pooled_output_v):
@@ -968,8 +1031,15 @@ class BertModel(BertPreTrainedModel):
         encoded_layers_t = [F.to_f32(t) for t in encoded_layers_t]
         encoded_layers_v = [F.to_f32(t) for t in encoded_layers_v]
         sequence_output_t, sequence_output_v = encoded_layers_t[-1], encoded_layers_v[-1]
-        pooled_output_t = self.t_pooler(sequence_output_t)
-        pooled_output_v = self.v_pooler(sequence_output_v)
+        if sequence_output_t.dim() == 2:
+            # the encoder ran its last layers on row maps (BertEncoder.forward `_last_layer_rows`): [rows, H] sequence outputs
+            # whose first len(batch) rows are the first row of every sample
+            n = input_txt.size(0)
+            pooled_output_t = self.t_pooler(sequence_output_t[:n].unsqueeze(1))
+            pooled_output_v = self.v_pooler(sequence_output_v[:n].unsqueeze(1))
+        else:
+            pooled_output_t = self.t_pooler(sequence_output_t)
+            pooled_output_v = self.v_pooler(sequence_output_v)
         if not output_all_encoded_layers:
             encoded_layers_t, encoded_layers_v = encoded_layers_t[-1], encoded_layers_v[-1]
         return encoded_layers_t, encoded_layers_v, pooled_output_t, pooled_output_v, all_attention_mask
@@ -1009,14 +1079,39 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
     def forward(self, input_ids, image_feat, image_loc, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, masked_lm_labels=None, image_label=None, image_target=None,
                 next_sentence_label=None, output_all_attention_masks=False):
-        sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
-            input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
-            output_all_encoded_layers=False, output_all_attention_masks=output_all_attention_masks)
         with_labels = not (masked_lm_labels is None or next_sentence_label is None or image_target is None)
+        # The layers behind the last connection layer are read at few rows only - row 0 of every sample (poolers) and the
+        # labelled rows (prediction heads): with the fixed-capacity gather those rows are known before the encoder runs (no
+        # host sync), and the output + feed-forward block of the last text / image layer runs on them alone (layers.py row
+        # maps). Every other step - the exact gather (its torch.nonzero would stall the launch queue in front of the last
+        # layer), inference, attention maps, the bf16 stream, fp8 / MX, `VB_LAST_LAYER_ROWS=0` - runs the whole layers.
+        gathered = None
+        if with_labels and image_label is not None and not output_all_attention_masks and self._static_gather() \
+                and self.training and torch.is_grad_enabled() and input_ids.is_cuda and layers.rows_enabled() \
+                and not _native.bf16_stream() and not _native.fp8_enabled() and not self.config.task_specific_tokens \
+                and self.bert.encoder.tail_takes_rows():
+            gathered = self._static_label_rows(masked_lm_labels, image_label)
+            batch, n_tok, n_reg_all = input_ids.size(0), input_ids.size(1), image_feat.size(1)
+            idx_t, n_t, idx_r, n_r = gathered[0], gathered[5], gathered[2], gathered[6]
+            idx_v = idx_r + torch.div(idx_r, n_reg_all - 1, rounding_mode="floor") + 1
+            map_t, head_t = _row_map(idx_t, n_t, batch, n_tok)
+            map_v, head_v = _row_map(idx_v, n_r, batch, n_reg_all)
+            last_layer_rows, gathered = (map_t, map_v), gathered + (head_t, head_v)
+        else:
+            last_layer_rows = None
+        encoder = self.bert.encoder
+        if last_layer_rows is not None:
+            encoder.__dict__["_last_layer_rows"] = last_layer_rows
+        try:
+            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
+                input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                output_all_encoded_layers=False, output_all_attention_masks=output_all_attention_masks)
+        finally:
+            encoder.__dict__.pop("_last_layer_rows", None)
         if with_labels and self.visual_target in (0, 1):
             losses = self._losses_at_labelled_positions(sequence_output_t, sequence_output_v, pooled_output_t,
                                                         pooled_output_v, masked_lm_labels, image_label,
-                                                        image_target, next_sentence_label)
+                                                        image_target, next_sentence_label, gathered)
             if losses is not None:
                 return losses
         prediction_scores_t, prediction_scores_v, seq_relationship_score = self.cls(
@@ -1043,56 +1138,76 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
                                              ignore_index=-1)
         return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
 
+    def _static_gather(self):
+        """This step gathers the labelled rows into fixed-capacity buffers (no host sync): see _losses_at_labelled_positions."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if not (self.label_capacity is not None or capturing) or self.visual_target != 0:
+            return False
+        # ("auto": the first step counts its labelled rows on the host and runs the exact gather)
+        return not (self.label_capacity == "auto" and self._auto_capacity is None and not capturing)
+
+    def _static_label_rows(self, masked_lm_labels, image_label):
+        """Index construction of the fixed-capacity gather -> (idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r): the
+        labelled rows are gathered into FIXED-capacity buffers (torch.nonzero_static), the host never learns the counts.
+        Padding rows carry label -1 / an all-zero target: they contribute nothing to the losses or to any gradient, and the
+        divisors are device scalars. Counts above the capacity would silently drop rows, so they are recorded for
+        check_label_capacity() (GraphedTrainStep polls it without stalling the device)."""
+        lm_flat = masked_lm_labels.reshape(-1)
+        labelled = image_label == 1
+        frac = self.label_capacity if self.label_capacity is not None else 0.25
+        if frac == "auto":
+            frac = self._auto_capacity if self._auto_capacity is not None else 0.25
+        cap_t = _capacity(lm_flat.numel(), frac)
+        cap_r = _capacity(labelled.numel(), frac)
+        mask_t = lm_flat != -1
+        idx_t = torch.nonzero_static(mask_t, size=cap_t, fill_value=0).squeeze(1)
+        n_t = mask_t.sum()
+        labels_t = torch.where(torch.arange(cap_t, device=idx_t.device) < n_t, lm_flat.index_select(0, idx_t),
+                               torch.full_like(idx_t, -1))
+        mask_r = labelled.reshape(-1)
+        idx_r = torch.nonzero_static(mask_r, size=cap_r, fill_value=0).squeeze(1)
+        n_r = mask_r.sum()
+        valid_r = torch.arange(cap_r, device=idx_r.device) < n_r
+        self._label_counts = (n_t, n_r, cap_t, cap_r)
+        # rows beyond the capacity are dropped by the gather: the divisor counts the rows actually used (so the
+        # region loss stays the mean over them instead of being scaled down), and a device-side sticky flag records
+        # the overflow (GraphedTrainStep reads it after every replay, check_label_capacity() on demand)
+        if self._label_overflow is None or self._label_overflow.device != n_t.device:
+            self._label_overflow = torch.zeros(1, dtype=torch.int32, device=n_t.device)
+        self._label_overflow.logical_or_(((n_t > cap_t) | (n_r > cap_r)).reshape(1))
+        divisor_r = torch.clamp(n_r, max=cap_r).to(torch.float32).reshape(1)
+        return idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r
+
     def _losses_at_labelled_positions(self, sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v,
-                                      masked_lm_labels, image_label, image_target, next_sentence_label):
+                                      masked_lm_labels, image_label, image_target, next_sentence_label, gathered=None):
         """The three pre-training losses with the heads evaluated ONLY where a label exists (~15 % of the
         tokens / regions): CrossEntropy(ignore_index=-1) ignores every other token row and the region loss
         multiplies every other region row by zero (reference vilbert.py:1506-1522,1578-1585), so the value
         and every gradient are the same while the [B,T,30522] logits tensor (1.1 GB at B=256) and 85 % of
         the two decoder GEMMs never exist. Costs one host sync for the row counts (the reference's training
         loop syncs every step anyway, train_concap.py:589-598). Returns None when nothing is labelled (the
-        caller then takes the reference-shaped path, which yields the reference's NaN)."""
+        caller then takes the reference-shaped path, which yields the reference's NaN).
+        gathered: forward() already built the fixed-capacity indices (_static_label_rows) and ran the last encoder layers on
+        _row_map() rows: the sequence outputs are [rows, H], the heads read them at _row_map()'s head indices."""
         cls = self.cls
         lm_flat = masked_lm_labels.reshape(-1)
         labelled = image_label == 1
-        n_reg_all = sequence_output_v.size(1)                       # regions incl. the global row 0
-        per = n_reg_all - 1
-        static = (self.label_capacity is not None or torch.cuda.is_current_stream_capturing()) and self.visual_target == 0
-        if static and self.label_capacity == "auto" and self._auto_capacity is None and not torch.cuda.is_current_stream_capturing():
+        per = labelled.reshape(labelled.size(0), -1).size(1)        # regions without the global row 0
+        static = gathered is not None or self._static_gather()
+        if not static and self.label_capacity == "auto" and self._auto_capacity is None and self.visual_target == 0:
             # "auto": the FIRST step counts its labelled rows on the host (one sync, the exact path below) and fixes the gather
             # capacity at 1.2 x the larger of the two labelled fractions (+ 1 % of the positions); every later step is
             # sync-free. check_label_capacity() - every k steps, off the hot path - raises if a batch ever exceeds it.
             frac = max(float((lm_flat != -1).sum()) / max(lm_flat.numel(), 1), float(labelled.sum()) / max(labelled.numel(), 1))
             self._auto_capacity = min(1.0, 1.2 * frac + 0.01)
-            static = False
         if static:
-            # Sync-free variant (HIP-graph capture, small per-GPU batches): the labelled rows are gathered into
-            # FIXED-capacity buffers (torch.nonzero_static), the host never learns the counts. Padding rows carry
-            # label -1 / an all-zero target: they contribute nothing to the losses or to any gradient, and the
-            # divisors are device scalars. Counts above the capacity would silently drop rows, so they are recorded
-            # for check_label_capacity() (GraphedTrainStep polls it without stalling the device).
-            frac = self.label_capacity if self.label_capacity is not None else 0.25
-            if frac == "auto":
-                frac = self._auto_capacity if self._auto_capacity is not None else 0.25
-            cap_t = _capacity(lm_flat.numel(), frac)
-            cap_r = _capacity(labelled.numel(), frac)
-            mask_t = lm_flat != -1
-            idx_t = torch.nonzero_static(mask_t, size=cap_t, fill_value=0).squeeze(1)
-            n_t = mask_t.sum()
-            labels_t = torch.where(torch.arange(cap_t, device=idx_t.device) < n_t, lm_flat.index_select(0, idx_t),
-                                   torch.full_like(idx_t, -1))
-            mask_r = labelled.reshape(-1)
-            idx_r = torch.nonzero_static(mask_r, size=cap_r, fill_value=0).squeeze(1)
-            n_r = mask_r.sum()
-            valid_r = torch.arange(cap_r, device=idx_r.device) < n_r
-            self._label_counts = (n_t, n_r, cap_t, cap_r)
-            # rows beyond the capacity are dropped by the gather: the divisor counts the rows actually used (so the
-            # region loss stays the mean over them instead of being scaled down), and a device-side sticky flag records
-            # the overflow (GraphedTrainStep reads it after every replay, check_label_capacity() on demand)
-            if self._label_overflow is None or self._label_overflow.device != n_t.device:
-                self._label_overflow = torch.zeros(1, dtype=torch.int32, device=n_t.device)
-            self._label_overflow.logical_or_(((n_t > cap_t) | (n_r > cap_r)).reshape(1))
-            divisor_r = torch.clamp(n_r, max=cap_r).to(torch.float32).reshape(1)
+            # sync-free variant (HIP-graph capture, small per-GPU batches): _static_label_rows
+            if gathered is None:
+                gathered = self._static_label_rows(masked_lm_labels, image_label)
+                compact = False
+            else:
+                compact = True
+            idx_t, labels_t, idx_r, valid_r, divisor_r = gathered[:5]
         else:
             idx_t = torch.nonzero(lm_flat != -1).squeeze(1)
             idx_r = torch.nonzero(labelled.reshape(-1)).squeeze(1)      # index into [B, n_reg_all - 1]
@@ -1101,6 +1216,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
             labels_t = lm_flat.index_select(0, idx_t)
             valid_r = None
             divisor_r = float(idx_r.numel())
+            compact = False
         idx_v = idx_r + torch.div(idx_r, per, rounding_mode="floor") + 1   # same rows inside [B, n_reg_all]
 
         pooled_output = _dropout(_fuse_pooled(cls.fusion_method, pooled_output_t, pooled_output_v), cls.dropout)
@@ -1110,10 +1226,16 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         next_sentence_loss = F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1),
                                              ignore_index=-1)
 
-        rows_t = sequence_output_t.reshape(-1, sequence_output_t.size(-1)).index_select(0, idx_t)
+        if compact:
+            rows_t = sequence_output_t.index_select(0, gathered[7])
+        else:
+            rows_t = sequence_output_t.reshape(-1, sequence_output_t.size(-1)).index_select(0, idx_t)
         masked_lm_loss = F.cross_entropy(cls.predictions(rows_t, pad_cols=True), labels_t, ignore_index=-1)
 
-        rows_v = sequence_output_v.reshape(-1, sequence_output_v.size(-1)).index_select(0, idx_v)
+        if compact:
+            rows_v = sequence_output_v.index_select(0, gathered[8])
+        else:
+            rows_v = sequence_output_v.reshape(-1, sequence_output_v.size(-1)).index_select(0, idx_v)
         scores_v = cls.imagePredictions(rows_v)
         target = image_target.reshape(-1, image_target.size(-1)).index_select(0, idx_r)
         if valid_r is not None:
