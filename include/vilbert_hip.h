@@ -439,7 +439,9 @@ int vb_additive_mask(void* stream, int64_t n, const void* mask, int32_t mask_is_
  * `batch` or 1 (broadcast; the 1-caption x N-images case of eval_retrieval, :1042-1053).
  * probs (may be NULL): [batch, heads, n_q, n_k] attention probabilities after dropout
  * (`visualization`, :451-458). lse (may be NULL): [batch, heads, n_q] log-sum-exp of the masked
- * scores (saved for backward). dropout_p in [0, 1): keep mask = f(seed, element index of probs).
+ * scores (saved for backward). dropout_p in [0, 1): keep mask = f(seed, element index of probs) =
+ * f(seed, ((b * heads + h) * n_q + q) * n_k + key) with THIS launch's n_k (a key chunk of a longer sequence, below,
+ * counts its own keys from 0: the caller gives every chunk its own seed).
  * head_dim in {32, 64, 128}; n_k <= VB_MAX_KEYS.
  *
  * vb_attention_bwd: given the same arguments (lse filled by the forward, probs ignored) and dO,

@@ -748,10 +748,22 @@ def _key_chunks(Sk):
     return [(c0, min(Sk, c0 + step)) for c0 in range(0, Sk, step)]
 
 
+CHUNK_SEED_STRIDE = 0xBF58476D1CE4E5B9
+
+
 def _chunk_seed(seed, c):
     """Dropout seed of key chunk c (the keep mask is a function of (seed, element index inside the launch): every chunk needs
-    its own seed, and backward must find it again from the node's one saved seed)."""
-    return (int(seed) + c * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF if seed else 0
+    its own seed, and backward must find it again from the node's one saved seed - a pure host function of (seed, c)).
+
+    Two launch seeds d apart draw the SAME mask, shifted by d / 0x9E3779B97F4A7C15 (mod 2^64, read as a signed number) elements:
+    csrc/rng.h hashes seed + index * 0x9E3779B97F4A7C15. An offset of c times that very stride - what this function used to
+    return - therefore made the mask of chunk c the mask of chunk 0 moved c keys to the left: one pattern for the whole row, not
+    one per chunk. The offset has to be a constant whose quotient by the hash's stride, in every combination with the strides
+    of the other seed sources (autograd_ops.next_seed per call, vb_seed_with_epoch per replay), stays far outside any index
+    range: with this one every two seeds within 8 chunks, 1024 calls and 8192 replays of each other are at least 2^36.6
+    elements apart (the largest mask of the models covers < 2^27; tests/test_dropout_mask.py checks the whole range).
+    Chunk 0 keeps the launch seed; seed 0 (dropout off) stays 0."""
+    return (int(seed) + c * CHUNK_SEED_STRIDE) & 0xFFFFFFFFFFFFFFFF if seed else 0
 
 
 def _attention_fwd_long(q, k, v, mask_add, heads, want_lse, drop_p=0.0, seed=0):
