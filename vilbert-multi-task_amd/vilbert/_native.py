@@ -376,6 +376,15 @@ TASK_SIGNATURES = {
     "vbt_argmax_pick": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _P, _I64]),
 }
 
+# include/vilbert_hip_pretrain.h (NCE masked-region loss of pre-training; prefix vbp_), mirrored one to one (checked by
+# tests/test_nce_index.py)
+PRETRAIN_SIGNATURES = {
+    "vbp_nce_negatives": (ctypes.c_int, [_P, _I64, _P, _I32, _I32, _I32, _I32, _U64, _P]),
+    "vbp_nce_workspace": (_I64, [_I64]),
+    "vbp_nce_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64]),
+    "vbp_nce_bwd": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _P, _P, _I64]),
+}
+
 _lib = None
 
 
@@ -389,7 +398,7 @@ def lib():
                 "g.build()'` (or `make -C vilbert-multi-task_amd/csrc`). There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
-                                  + list(TASK_SIGNATURES.items())):
+                                  + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

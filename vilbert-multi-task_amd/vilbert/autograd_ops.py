@@ -536,6 +536,28 @@ class BCEWithLogitsFn(torch.autograd.Function):
         return ops.bce_bwd(grad_loss, logits, target), None
 
 
+class NCERegionFn(torch.autograd.Function):
+    """NCE masked-region loss, visual_target == 2 - reference :1523-1575. The negatives are a pure function of (seed, labelled
+    region, draw) (csrc/nce_index.h); the seed is drawn from next_seed() unless given and kept on the node. The forward
+    leaves the unscaled gradient behind (ops.nce_fwd), so the backward is one scale; the target table gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, predict, table, idx_r, valid, count, batch, regions, n_across, n_inside, seed=None):
+        seed = next_seed() if seed is None else seed
+        neg = ops.nce_negatives(idx_r, batch, regions, n_across, n_inside, seed)
+        loss, dsave = ops.nce_fwd(predict, table, idx_r, neg, valid, count, want_grad=True)
+        ctx.seed = seed
+        ctx.valid = valid
+        ctx.save_for_backward(dsave, count)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        dsave, count = ctx.saved_tensors
+        return (ops.nce_bwd(grad_loss, dsave, ctx.valid, count),) + (None,) * 9
+
+
 class CastFn(Function):
     """fp32 <-> bfloat16 at the edges of the bf16 stream (embeddings in, sequence outputs out); backward = the other cast."""
 

@@ -189,3 +189,20 @@ def kl_div_log_softmax(scores, target, divisor):
     if _needs_grad(scores):
         return A.KLDivFn.apply(scores, target, divisor)
     return ops.kl_fwd(scores, target, divisor)[0]
+
+
+def nce_region_loss(predict_rows, image_target, idx_r, valid_r, count, batch, regions, n_across, n_inside, seed=None):
+    """NCE masked-region loss (visual_target == 2, reference vilbert.py:1523-1575) -> 0-dim loss. predict_rows [rows, dim]: the
+    image head's output at the labelled regions idx_r (= b * regions + r, regions without the global row); image_target: the
+    [batch, regions, dim] (or flat [batch * regions, dim]) target features, no gradient; valid_r: bool flag per row or None
+    (padding rows of the fixed-capacity gather); count: 1-element fp32 device tensor, the divisor. Each row is contrasted with
+    n_across regions of other samples and n_inside other regions of its own sample, drawn by csrc/nce_index.h from `seed`
+    (default: autograd_ops.next_seed()) and the registered device step counter."""
+    table = image_target.reshape(-1, image_target.size(-1))
+    if table.size(0) != batch * regions:
+        raise RuntimeError("nce_region_loss: image_target does not hold batch * regions rows")
+    if _needs_grad(predict_rows):
+        return A.NCERegionFn.apply(predict_rows, table, idx_r, valid_r, count, batch, regions, n_across, n_inside, seed)
+    seed = A.next_seed() if seed is None else seed
+    neg = ops.nce_negatives(idx_r, batch, regions, n_across, n_inside, seed)
+    return ops.nce_fwd(predict_rows, table, idx_r, neg, valid_r, count, want_grad=False)[0]

@@ -1021,3 +1021,69 @@ def argmax_pick(logits, labels, want_dense=False):
                                     N.dev_f32(l, "argmax_pick labels"), ldl, idx.data_ptr(), picked.data_ptr(),
                                     dense.data_ptr() if want_dense else None, n), "vbt_argmax_pick")
     return idx, picked, dense
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# NCE masked-region loss of pre-training (visual_target == 2; csrc/nce.hip, include/vilbert_hip_pretrain.h)
+# ---------------------------------------------------------------------------------------------------------------
+def _valid_bytes(valid, rows):
+    """Address of the one-byte-per-row flags (None = every row valid) and the tensor that keeps them alive."""
+    if valid is None:
+        return None, None
+    if valid.dtype == torch.bool:
+        valid = _contig(valid).view(torch.uint8)
+    if not valid.is_cuda or valid.dtype != torch.uint8 or valid.numel() != rows:
+        raise RuntimeError("nce: expected one bool / uint8 flag per row on a HIP device")
+    valid = _contig(valid)
+    return valid.data_ptr(), valid
+
+
+def nce_negatives(region_idx, batch, regions, n_across, n_inside, seed):
+    """[rows, n_across + n_inside] int64 table rows of the negatives of the labelled regions region_idx (= b * regions + r;
+    regions without the global row): csrc/nce_index.h under `seed` (and the registered device step counter). One launch."""
+    region_idx = _contig(region_idx)
+    rows = region_idx.numel()
+    out = torch.empty(rows, n_across + n_inside, dtype=torch.int64, device=region_idx.device)
+    N.check(N.lib().vbp_nce_negatives(N.stream_ptr(), rows, N.dev_i64(region_idx, "nce region index"), batch, regions, n_across,
+                                      n_inside, seed & 0xFFFFFFFFFFFFFFFF, out.data_ptr()), "vbp_nce_negatives")
+    return out
+
+
+def nce_fwd(predict, table, pos_idx, neg_idx, valid, count, want_grad=True):
+    """Cross entropy (class 0) of <table[pos], predict>, <table[neg_j], predict> per row, summed over the valid rows and
+    divided by the 1-element fp32 device tensor `count`. predict [rows, dim] and table [table_rows, dim]: fp32, row strides
+    allowed. Returns (loss 0-dim, dsave [rows, dim] - the unscaled gradient for nce_bwd - or None)."""
+    if predict.dim() != 2 or table.dim() != 2 or predict.shape[1] != table.shape[1]:
+        raise RuntimeError("nce: expected predict [rows, dim] and table [table_rows, dim]")
+    if not _row_strided(predict):
+        predict = _contig(predict)
+    if not _row_strided(table):
+        table = _contig(table)
+    rows, dim = predict.shape
+    pos_idx, neg_idx = _contig(pos_idx), _contig(neg_idx)
+    if pos_idx.numel() != rows or neg_idx.dim() != 2 or neg_idx.shape[0] != rows:
+        raise RuntimeError("nce: expected pos_idx [rows] and neg_idx [rows, n_neg]")
+    count = _contig(count.reshape(1))
+    vp, _keep = _valid_bytes(valid, rows)
+    lib = N.lib()
+    out = torch.empty(1 + int(lib.vbp_nce_workspace(rows)), dtype=torch.float32, device=predict.device)   # {loss, partials}
+    dsave = torch.empty(rows, dim, dtype=torch.float32, device=predict.device) if want_grad else None
+    ldp = predict.stride(0) if rows > 1 else dim
+    ldt = table.stride(0) if table.shape[0] > 1 else dim
+    N.check(lib.vbp_nce_fwd(N.stream_ptr(), rows, dim, neg_idx.shape[1], N.dev_f32(predict, "nce predict"), ldp,
+                            N.dev_f32(table, "nce target table"), table.shape[0], ldt, N.dev_i64(pos_idx, "nce pos_idx"),
+                            N.dev_i64(neg_idx, "nce neg_idx"), vp, N.dev_f32(count, "nce count"), out.data_ptr() + 4,
+                            out.data_ptr(), dsave.data_ptr() if want_grad else None, dim), "vbp_nce_fwd")
+    return out[0], dsave
+
+
+def nce_bwd(grad_loss, dsave, valid, count):
+    """dpredict [rows, dim] = grad_loss / count * dsave, exact zeros on invalid rows. One launch."""
+    rows, dim = dsave.shape
+    grad_loss, count = _contig(grad_loss).reshape(1), _contig(count.reshape(1))
+    vp, _keep = _valid_bytes(valid, rows)
+    d = torch.empty_like(dsave)
+    N.check(N.lib().vbp_nce_bwd(N.stream_ptr(), rows, dim, N.dev_f32(dsave, "nce dsave"), dim, vp,
+                                N.dev_f32(grad_loss, "nce grad"), N.dev_f32(count, "nce count"), d.data_ptr(), dim),
+            "vbp_nce_bwd")
+    return d

@@ -25,6 +25,7 @@ from torch.nn import CrossEntropyLoss
 import torch.nn.functional as TF
 
 from . import _native
+from . import autograd_ops as A
 from . import functional as F
 from . import layers
 from . import ops
@@ -1063,6 +1064,8 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         self._auto_capacity = None
         self._label_counts = None
         self._label_overflow = None     # device flag: a fixed-capacity label gather dropped rows (sticky until checked)
+        self._nce_seed = None           # host seed of the last native NCE region loss (visual_target == 2): its negatives
+                                        # are csrc/nce_index.h of it (and of the registered device step counter)
         self.loss_fct = CrossEntropyLoss(ignore_index=-1)
         print("model's visual target is ", config.visual_target)
         if self.visual_target == 0:
@@ -1086,7 +1089,8 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         # maps). Every other step - the exact gather (its torch.nonzero would stall the launch queue in front of the last
         # layer), inference, attention maps, the bf16 stream, fp8 / MX, `VB_LAST_LAYER_ROWS=0` - runs the whole layers.
         gathered = None
-        if with_labels and image_label is not None and not output_all_attention_masks and self._static_gather() \
+        native_losses = with_labels and (self.visual_target in (0, 1) or self._nce_native(image_feat, image_target))
+        if native_losses and image_label is not None and not output_all_attention_masks and self._static_gather() \
                 and self.training and torch.is_grad_enabled() and input_ids.is_cuda and layers.rows_enabled() \
                 and not _native.bf16_stream() and not _native.fp8_enabled() and not self.config.task_specific_tokens \
                 and self.bert.encoder.tail_takes_rows():
@@ -1108,7 +1112,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
                 output_all_encoded_layers=False, output_all_attention_masks=output_all_attention_masks)
         finally:
             encoder.__dict__.pop("_last_layer_rows", None)
-        if with_labels and self.visual_target in (0, 1):
+        if native_losses:
             losses = self._losses_at_labelled_positions(sequence_output_t, sequence_output_v, pooled_output_t,
                                                         pooled_output_v, masked_lm_labels, image_label,
                                                         image_target, next_sentence_label, gathered)
@@ -1141,10 +1145,20 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
     def _static_gather(self):
         """This step gathers the labelled rows into fixed-capacity buffers (no host sync): see _losses_at_labelled_positions."""
         capturing = torch.cuda.is_current_stream_capturing()
-        if not (self.label_capacity is not None or capturing) or self.visual_target != 0:
+        if not (self.label_capacity is not None or capturing):
             return False
         # ("auto": the first step counts its labelled rows on the host and runs the exact gather)
         return not (self.label_capacity == "auto" and self._auto_capacity is None and not capturing)
+
+    def _nce_native(self, image_feat, image_target):
+        """visual_target == 2 takes the native NCE loss (csrc/nce.hip) at the labelled rows: fp32 HIP tensors, no gradient
+        wanted for the targets, at least two samples and two regions (an "across" negative needs another sample, an "inside"
+        one another region). Everything else - CPU tensors, `VB_NCE_NATIVE=0` - keeps the reference-shaped _nce_region_loss."""
+        if self.visual_target != 2 or os.environ.get("VB_NCE_NATIVE", "1") == "0":
+            return False
+        return (image_target.is_cuda and image_feat.is_cuda and image_target.dtype == torch.float32
+                and image_feat.dtype == torch.float32 and not image_target.requires_grad and image_target.dim() == 3
+                and image_target.size(0) >= 2 and image_target.size(1) >= 2)
 
     def _static_label_rows(self, masked_lm_labels, image_label):
         """Index construction of the fixed-capacity gather -> (idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r): the
@@ -1194,7 +1208,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         labelled = image_label == 1
         per = labelled.reshape(labelled.size(0), -1).size(1)        # regions without the global row 0
         static = gathered is not None or self._static_gather()
-        if not static and self.label_capacity == "auto" and self._auto_capacity is None and self.visual_target == 0:
+        if not static and self.label_capacity == "auto" and self._auto_capacity is None:
             # "auto": the FIRST step counts its labelled rows on the host (one sync, the exact path below) and fixes the gather
             # capacity at 1.2 x the larger of the two labelled fractions (+ 1 % of the positions); every later step is
             # sync-free. check_label_capacity() - every k steps, off the hot path - raises if a batch ever exceeds it.
@@ -1237,12 +1251,28 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         else:
             rows_v = sequence_output_v.reshape(-1, sequence_output_v.size(-1)).index_select(0, idx_v)
         scores_v = cls.imagePredictions(rows_v)
+        if self.visual_target == 2:
+            # NCE against sampled negative region features (csrc/nce.hip): the candidate rows are read in place in the flat
+            # target table, the negatives are a function of (seed, region) - the same for either gather
+            count = divisor_r if torch.is_tensor(divisor_r) else torch.full((1,), divisor_r, dtype=torch.float32,
+                                                                          device=scores_v.device)
+            self._nce_seed = A.next_seed()
+            masked_img_loss = F.nce_region_loss(scores_v, image_target, idx_r, valid_r, count, image_target.size(0), per,
+                                                int(self.num_negative * 0.7), int(self.num_negative * 0.3),
+                                                seed=self._nce_seed)
+            return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
         target = image_target.reshape(-1, image_target.size(-1)).index_select(0, idx_r)
         if valid_r is not None:
             target = target * valid_r.unsqueeze(1).to(target.dtype)     # padding rows: all-zero target
         if self.visual_target == 1:
-            masked_img_loss = torch.sum(self.vis_criterion(scores_v, target)) / max(
-                torch.sum(labelled.unsqueeze(2).expand(-1, -1, image_target.size(-1))), 1)
+            if valid_r is not None:
+                # a zero target does not silence a padding row of the squared error: the row's terms are multiplied by
+                # zero (so it gets no gradient either); the divisor stays on the device: max(rows used * dim, 1)
+                sq = self.vis_criterion(scores_v, target) * valid_r.unsqueeze(1).to(scores_v.dtype)
+                masked_img_loss = torch.sum(sq) / torch.clamp(divisor_r * float(image_target.size(-1)), min=1.0).squeeze(0)
+            else:
+                masked_img_loss = torch.sum(self.vis_criterion(scores_v, target)) / max(
+                    torch.sum(labelled.unsqueeze(2).expand(-1, -1, image_target.size(-1))), 1)
         else:
             # divisor: the reference's max(sum(image_label == 1), 0) (:1520-1522) = the number of rows here
             masked_img_loss = F.kl_div_log_softmax(scores_v, target, divisor_r)
