@@ -591,7 +591,8 @@ int vb_concap_finish_batch(void* stream, const vb_concap_batch* a);
  *     residual (bf16 [M][N]):  dropout(v, dropout_p, seed) + residual   (mask element index = m * N + n, rng.h - the
  *         index vb_layernorm_bwd_bf16 regenerates it from; dropout only together with a residual);
  *     mul (bf16 [M][N]):       v * mul   (dgrad through an activation whose derivative the forward saved);
- *   written as bf16 to C (ldc % 2 == 0) or as fp32 to C32 (plain / residual / RELU only). Rows >= M are never stored.
+ *   written as bf16 to C (ldc % 8 == 0, C 16-byte aligned) or as fp32 to C32 (ldc32 % 4 == 0, C32 16-byte aligned; plain /
+ *   residual / RELU only). residual / mul / act_grad: ld % 8 == 0, 16-byte aligned, as is every bias. Rows >= M are never stored.
  * vb_wgrad_bf16:   dW_s[seg_n][K] += dY[:, s seg_n : (s + 1) seg_n]^T X   for the nseg stacked segments of dY [M][nseg seg_n]
  *   (contraction over the M rows: row-major tiles in LDS, fragments by the transposing LDS read ds_read_b64_tr_b16), fp32
  *   atomics into dW (the gradient-arena slices: zero-filled once per backward pass, or holding an earlier contribution);
@@ -654,7 +655,8 @@ typedef struct {
     const uint16_t* W;
     int64_t ldw;
     const float* bias[VB_MAX_SEGMENTS]; /* bias of output columns [s N / bias_segments, (s + 1) N / bias_segments), or NULL */
-    int32_t bias_segments;      /* 0 or 1: one bias of N values; stacked weights pass their nn.Linear biases unpacked */
+    int32_t bias_segments;      /* 0 = one bias of N values, else up to VB_MAX_SEGMENTS equal segments (stacked weights pass
+                                   their nn.Linear biases unpacked) */
     uint16_t* C;                /* bf16 out, or NULL */
     int64_t ldc;
     float* C32;                 /* fp32 out, or NULL (exactly one of C / C32) */
