@@ -784,16 +784,20 @@ typedef struct {
      * input-gradient chain of the block run on M COMPACT rows: compact row r stands for row row_map[r] of the full
      * [src_rows, .] tensors ctx and x, -1 = padding row (zeros in, nothing written back); a full row is named at most once.
      * The dropout masks are those of the full tensor (indexed by the source row). sum1 ... y, dy and the d_* buffers have M
-     * rows. Every reduction over rows (weight, bias and LayerNorm gradients) runs at full size on zero-expanded operands in
-     * full_ws, in the order of the unmapped block: those gradients are bit for bit the ones of the block on every row with
-     * zero dy at the rows the map does not name. Backward also writes the full-size gradients the attention block reads
-     * (mapped rows: their values, all others 0; every row written once). ln_ws: sized for src_rows rows. */
+     * rows. Backward runs on the compact rows too, the reductions over rows (weight, bias and LayerNorm gradients)
+     * included: a row the map does not name has a zero dy in the whole block, so these gradients are the ones of the block
+     * on every row up to the grouping of one fp32 sum (deterministic from run to run). A padding entry must come with a zero
+     * dy row; the forward buffers of its row are finite, so it adds exact zeros. Only the two gradients the attention block
+     * reads are written at full size (mapped rows: their values, all others 0; every row written once). ln_ws: sized for M
+     * rows or more. */
     const int32_t* row_map;                    /* [M] device */
     int64_t src_rows;
     void* ctx_rows;                            /* [M, Hc] the gathered context rows (forward scratch) */
     void* d_ctx_full;                          /* backward: [src_rows, Hc] */
     void* d_sum1_full;                         /* backward: [src_rows, H] */
-    float* full_ws;                            /* backward scratch: src_rows * (8 H + 2 I + 5) floats, 16-byte aligned */
+    float* full_ws;                            /* backward scratch, required, 16-byte aligned: src_rows 32-bit words (the
+                                                * inverse map); the size is not validated, and a larger buffer - up to the
+                                                * former src_rows * (8 H + 2 I + 5) floats - is accepted */
 } vb_ffn_block;
 
 typedef struct {

@@ -31,15 +31,14 @@ namespace vbrows {
 // row kernels of an output + feed-forward block that runs on a subset of its rows (rowmap.hip; fp32, cols % 4 == 0):
 // map[r] = the row of the full tensor compact row r stands for, -1 = padding row
 int gather(hipStream_t st, long M, int cols, const float* src, const int32_t* map, long src_rows, float* out);
-// out[r] = dropout(lin[r], p, mask of full row map[r]) + res[res_mapped ? map[r] : r] (res may be null; out may be lin)
+// out[r] = dropout(lin[r], p, mask of full row map[r]) + res[res_mapped ? map[r] : r] (out may be lin); res null: the
+// dropped twin of a compact gradient, out[r] = keep(seed, map[r] cols + col) ? lin[r] / (1 - p) : 0, padding rows zeros
 int drop_add(hipStream_t st, long M, int cols, const float* lin, const float* res, bool res_mapped, const int32_t* map,
              long src_rows, float* out, float p, uint64_t seed);
 // inv[R] = the compact row with map[r] == R (the first, should there be more), or -1
 int invert(hipStream_t st, long src_rows, long M, const int32_t* map, int32_t* inv);
-// full[R] = compact[inv[R]], zeros where inv[R] < 0; scatter_stats: four [M] vectors -> full[4][src_rows]
+// full[R] = compact[inv[R]], zeros where inv[R] < 0
 int scatter(hipStream_t st, long src_rows, int cols, const float* compact, const int32_t* inv, float* full);
-int scatter_stats(hipStream_t st, long src_rows, const float* v0, const float* v1, const float* v2, const float* v3,
-                  const int32_t* inv, float* full);
 }  // namespace vbrows
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -316,52 +316,49 @@ int ffn_block_rows_fwd(void* st, const vb_ffn_block& f, bool training) {
     return ln_fwd<kF32>(st, M, f.H, sum2, f.ln2, f.eps, f.y, training ? f.mean2 : nullptr, training ? f.rstd2 : nullptr);
 }
 
-// Backward: the input-gradient chain (three GEMMs) runs on the compact rows; every reduction over rows - the three weight /
-// bias gradients, the LayerNorm parameter gradients - runs at FULL size, on operands expanded with zero rows into full_ws,
-// by the launches of the unmapped block: a zero dy row adds exact zeros, so these gradients are those of the block on every
-// row bit for bit (a compact reduction would add the same terms in another grouping). The LayerNorm backward at full size
-// also yields d_sum1 as the attention block reads it and the dropped twins with the masks of the full tensor.
+// Backward: everything the block computes runs on the M COMPACT rows - both LayerNorm backwards (with the compact statistics
+// of forward) and their column reduces, the three input-gradient GEMMs, and the three weight / bias gradients, which contract
+// over M rows of the compact operands (ctx_rows is still in the saved forward buffer). A row the map does not name has a zero
+// dy in the whole block and adds nothing there; here it is simply absent, so the ten parameter gradients of the block are
+// the whole block's up to the grouping of one fp32 sum (fewer, other partial sums over rows; deterministic from run to run).
+// A padding entry has a zero dy and finite forward buffers (zeros in sum1 / sum2 / ctx_rows, beta in a1, gelu(W1 beta + b1)
+// in h; its statistics are mean 0, rstd 1 / sqrt(eps)), so it adds exact zeros to every reduction.
+// The dropped twins carry the mask of the FULL tensor (element map[r] H + col): the row kernel draws them, as in forward;
+// layernorm_bwd_kernel, which would index the mask by the compact row, runs without its twin.
+// FULL size: only d_sum1_full and d_ctx_full, which the attention block reads - the compact d_sum1 / d_ctx scattered through
+// the inverse map (the first src_rows words of full_ws), zeros at every row no entry names.
 int ffn_block_rows_bwd(void* st, WgradQueue& wq, const vb_ffn_block& f) {
     hipStream_t hs = static_cast<hipStream_t>(st);
     const long M = f.M, R = f.src_rows;
-    const vbrows::FullWs w(R, f.H, f.I);
-    float* ws = f.full_ws;
-    int32_t* inv = reinterpret_cast<int32_t*>(ws + w.inv);
-    float* stats = ws + w.stats;
+    int32_t* inv = reinterpret_cast<int32_t*>(f.full_ws);
     auto compact = [](const void* p) { return static_cast<const float*>(p); };
-    VB_TRY(vbrows::invert(hs, R, M, f.row_map, inv));
-    VB_TRY(vbrows::scatter_stats(hs, R, f.mean1, f.rstd1, f.mean2, f.rstd2, inv, stats));
     // y = LN(sum2)
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.dy), inv, ws + w.dy));
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.sum2), inv, ws + w.sum2));
-    VB_TRY(ln_bwd<kF32>(st, R, f.H, ws + w.dy, ws + w.sum2, stats + 2 * R, stats + 3 * R, f.ln2, ws + w.d_sum2, f.ln_ws,
-                        ws + w.d_sum2_drop, f.p_f, f.seed_f));
-    const float* dyd_full = f.p_f > 0.f ? ws + w.d_sum2_drop : ws + w.d_sum2;
-    VB_TRY(vbrows::gather(hs, M, f.H, ws + w.d_sum2, f.row_map, R, static_cast<float*>(f.d_sum2)));
+    VB_TRY(ln_bwd<kF32>(st, M, f.H, f.dy, f.sum2, f.mean2, f.rstd2, f.ln2, f.d_sum2, f.ln_ws, nullptr, 0.f, 0));
     const void* dyd = f.d_sum2;
     if (f.p_f > 0.f) {
-        VB_TRY(vbrows::gather(hs, M, f.H, dyd_full, f.row_map, R, static_cast<float*>(f.d_sum2_drop)));
+        VB_TRY(vbrows::drop_add(hs, M, f.H, compact(f.d_sum2), nullptr, false, f.row_map, R, static_cast<float*>(f.d_sum2_drop),
+                                f.p_f, f.seed_f));
         dyd = f.d_sum2_drop;
     }
     // sum2 = dropout(h W2^T + b2) + a1;  h = gelu(pre)
     VB_TRY(dgrad<kF32>(st, M, f.f2, dyd, f.d_pre, nullptr, f.dact));
-    VB_TRY(vbrows::scatter(hs, R, f.I, compact(f.h), inv, ws + w.h));
-    wq.push(R, f.f2, dyd_full, ws + w.h);
+    wq.push(M, f.f2, dyd, f.h);
     VB_TRY(dgrad<kF32>(st, M, f.f1, f.d_pre, f.d_a1, f.d_sum2, nullptr));
-    VB_TRY(vbrows::scatter(hs, R, f.I, compact(f.d_pre), inv, ws + w.d_pre));
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.a1), inv, ws + w.a1));
-    wq.push(R, f.f1, ws + w.d_pre, ws + w.a1);
-    // a1 = LN(sum1): d_sum1 at full size is what the attention block reads
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.d_a1), inv, ws + w.d_a1));
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.sum1), inv, ws + w.sum1));
-    VB_TRY(ln_bwd<kF32>(st, R, f.H, ws + w.d_a1, ws + w.sum1, stats, stats + R, f.ln1, f.d_sum1_full, f.ln_ws,
-                        ws + w.d_sum1_drop, f.p_o, f.seed_o));
-    const float* dod_full = f.p_o > 0.f ? ws + w.d_sum1_drop : static_cast<const float*>(f.d_sum1_full);
-    float* dod = static_cast<float*>(f.p_o > 0.f ? f.d_sum1_drop : f.d_sum1);
-    VB_TRY(vbrows::gather(hs, M, f.H, dod_full, f.row_map, R, dod));
+    wq.push(M, f.f1, f.d_pre, f.a1);
+    // a1 = LN(sum1)
+    VB_TRY(ln_bwd<kF32>(st, M, f.H, f.d_a1, f.sum1, f.mean1, f.rstd1, f.ln1, f.d_sum1, f.ln_ws, nullptr, 0.f, 0));
+    const void* dod = f.d_sum1;
+    if (f.p_o > 0.f) {
+        VB_TRY(vbrows::drop_add(hs, M, f.H, compact(f.d_sum1), nullptr, false, f.row_map, R, static_cast<float*>(f.d_sum1_drop),
+                                f.p_o, f.seed_o));
+        dod = f.d_sum1_drop;
+    }
     // sum1 = dropout(ctx Wo^T + bo) + x
     VB_TRY(dgrad<kF32>(st, M, f.o, dod, f.d_ctx, nullptr, nullptr));
-    wq.push(R, f.o, dod_full, f.ctx);
+    wq.push(M, f.o, dod, f.ctx_rows);
+    // what the attention block reads, at full size
+    VB_TRY(vbrows::invert(hs, R, M, f.row_map, inv));
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.d_sum1), inv, static_cast<float*>(f.d_sum1_full)));
     return vbrows::scatter(hs, R, f.Hc, compact(f.d_ctx), inv, static_cast<float*>(f.d_ctx_full));
 }
 

@@ -7,8 +7,10 @@
 
 namespace vbrows {
 
-// Layout of vb_ffn_block.full_ws (floats; R = src_rows): the zero-expanded operands of the full-size reductions of a mapped
-// block's backward. Every [R, .] array starts on a 16-byte boundary (H, I multiples of 4); the per-row words come last.
+// Layout of vb_ffn_block.full_ws (floats; R = src_rows) of a mapped block's backward that ran its reductions over rows at full
+// size on zero-expanded operands. Every [R, .] array starts on a 16-byte boundary (H, I multiples of 4); the per-row words
+// come last. The backward now reduces over the compact rows and uses the FIRST R words of full_ws only (the inverse map): the
+// size of full_ws is not validated, so a caller may pass R words, or a buffer of this layout as before.
 struct FullWs {
     long dy, sum2, sum1, a1, h, d_sum2, d_sum2_drop, d_pre, d_a1, d_sum1_drop, stats, inv, total;
     FullWs(long R, long H, long I) {

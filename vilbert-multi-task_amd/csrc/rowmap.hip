@@ -1,7 +1,8 @@
 // Row kernels of an output + feed-forward block that runs on a SUBSET of its rows (vb_ffn_block.row_map; layers.hip):
 //   gather        out[r] = src[map[r]]                                    (padding rows, map[r] = -1: zeros)
 //   drop + add    out[r] = dropout(lin[r]) + res[map[r] or r]             (the dropout / residual epilogue of the GEMMs, with
-//                                                                          the mask of the FULL tensor: keep(seed, map[r] N + col))
+//                                                                          the mask of the FULL tensor: keep(seed, map[r] N + col);
+//                                                                          without res: the dropped twin of a compact gradient)
 //   invert        inv[R] = the r with map[r] == R, or -1
 //   scatter       full[R] = compact[inv[R]]                               (rows no compact row stands for: zeros)
 // fp32, 16-byte accesses (cols % 4 == 0). The GEMM and LayerNorm kernels themselves know nothing of the map.
@@ -79,19 +80,6 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(long src_rows, int co
     }
 }
 
-// the same for four per-row scalars (LayerNorm statistics): full[k][R] = v_k[inv[R]] or 0
-__global__ __launch_bounds__(256) void scatter_stats_kernel(long src_rows, const float* __restrict__ v0, const float* __restrict__ v1,
-                                                            const float* __restrict__ v2, const float* __restrict__ v3,
-                                                            const int32_t* __restrict__ inv, float* __restrict__ full) {
-    for (long R = (long)blockIdx.x * blockDim.x + threadIdx.x; R < src_rows; R += (long)gridDim.x * blockDim.x) {
-        const long r = inv[R];
-        full[R] = r >= 0 ? v0[r] : 0.f;
-        full[src_rows + R] = r >= 0 ? v1[r] : 0.f;
-        full[2 * src_rows + R] = r >= 0 ? v2[r] : 0.f;
-        full[3 * src_rows + R] = r >= 0 ? v3[r] : 0.f;
-    }
-}
-
 inline unsigned grid_for(long work_items) {
     long blocks = (work_items + 255) / 256;
     if (blocks > 2048) blocks = 2048;
@@ -128,13 +116,6 @@ int invert(hipStream_t st, long src_rows, long M, const int32_t* map, int32_t* i
 int scatter(hipStream_t st, long src_rows, int cols, const float* compact, const int32_t* inv, float* full) {
     hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(src_rows * (cols / 4))), dim3(256), 0, st, src_rows, cols / 4,
                        reinterpret_cast<const f32x4*>(compact), inv, reinterpret_cast<f32x4*>(full));
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-int scatter_stats(hipStream_t st, long src_rows, const float* v0, const float* v1, const float* v2, const float* v3,
-                  const int32_t* inv, float* full) {
-    hipLaunchKernelGGL(scatter_stats_kernel, dim3(grid_for(src_rows)), dim3(256), 0, st, src_rows, v0, v1, v2, v3, inv, full);
     VB_LAUNCH_CHECK();
     return 0;
 }

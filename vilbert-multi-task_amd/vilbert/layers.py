@@ -382,7 +382,7 @@ def _self_plan(p, adims, dims, b16, training, row_cap=None):
     if row_cap is not None:
         t.add("d_sum1_rows", Mb * H * es)
         t.add("d_ctx_rows", Mb * H * es)
-        t.add("full_ws", M * (8 * H + 2 * I + 5) * 4)       # (vb_ffn_block.full_ws: operands of the full-size reductions)
+        t.add("full_ws", M * 4)                             # (vb_ffn_block.full_ws: the inverse map, one int32 per row of x)
     t.add("dqkv", M * 3 * H * es)
     t.add("dvec", B * heads * S * 4)
     a = N.LayerArgs()
@@ -401,8 +401,8 @@ class SelfLayerFn(Function):
     dyn = (p_o, p_f, seed_o, seed_f, p1, seed1)
     rows: None, or the int32 row map of the output + FFN block (vb_ffn_block.row_map: compact row -> row of x, -1 = padding;
     at most the plan's row_cap entries, a row of x at most once): y is then [len(rows), H] and the rows of x no entry names
-    get a zero gradient from the block - the attention part still runs on every row, and the parameter gradients are bit for
-    bit those of the whole layer with a zero dy at the other rows."""
+    get a zero gradient from the block - the attention part still runs on every row, and the parameter gradients are those of
+    the whole layer with a zero dy at the other rows (the block's own ten up to the grouping of one fp32 sum over rows)."""
 
     @staticmethod
     def forward(ctx, x, mask, rows, plan, dyn, *p):
@@ -450,11 +450,11 @@ class SelfLayerFn(Function):
         if rows is None:
             _dyn_ffn_bwd(a.s1, t, tbase, dy.data_ptr(), d_sum1, d_ctx, tg, 6, _ln_ws(dev, M, H, b16), dyn)
         else:
-            # the block's input-gradient chain is compact; its reductions over rows (weight / LayerNorm gradients) run at
-            # full size in full_ws, and it writes the full-size gradients the attention block reads
+            # the block's backward is compact, its reductions over rows (weight / LayerNorm gradients) too; it writes the
+            # full-size gradients the attention block reads through the inverse map in full_ws
             f = a.s1
             _dyn_ffn_bwd(f, t, tbase, dy.data_ptr(), t.at(tbase, "d_sum1_rows"), t.at(tbase, "d_ctx_rows"), tg, 6,
-                         _ln_ws(dev, M, H, b16), dyn)
+                         _ln_ws(dev, max(M, rows.numel()), H, b16), dyn)
             f.M, f.row_map, f.ctx_rows = rows.numel(), rows.data_ptr(), c.at(base, "ctx_rows")
             f.d_sum1_full, f.d_ctx_full = d_sum1, d_ctx
             f.full_ws = t.at(tbase, "full_ws")
