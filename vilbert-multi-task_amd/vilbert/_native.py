@@ -385,6 +385,22 @@ PRETRAIN_SIGNATURES = {
     "vbp_nce_bwd": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _P, _P, _I64]),
 }
 
+# include/vilbert_hip_heads.h (row kernels of the pre-training poolers, heads and losses on the bf16 stream; prefix vbh_),
+# mirrored one to one (checked by tests/test_heads16_abi.py)
+HEADS_SIGNATURES = {
+    "vbh_padded": (_I64, [_I64]),
+    "vbh_gather_rows_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I64, _P, _P, _I64]),
+    "vbh_invert_map": (ctypes.c_int, [_P, _I64, _I64, _P, _P]),
+    "vbh_scatter_rows_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _I64, _P, _P, _I64]),
+    "vbh_weight_shadow_ragged": (ctypes.c_int, [_P, _I32, _I32, _P, _I64, _P, _P, _P, _P]),
+    "vbh_xent_bwd_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _P, _P, _I64, _P, _I64, _P]),
+    "vbh_colsum_parts_count": (_I64, [_I64]),
+    "vbh_colsum_parts": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P]),
+    "vbh_kl_bwd_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _P, _P, _F32, _P, _P, _I64]),
+    "vbh_relu_bwd_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _I64]),
+    "vbh_mul_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _I64]),
+}
+
 _lib = None
 
 
@@ -398,7 +414,8 @@ def lib():
                 "g.build()'` (or `make -C vilbert-multi-task_amd/csrc`). There is no fallback path." % LIB_PATH)
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
-                                  + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())):
+                                  + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
+                                  + list(HEADS_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

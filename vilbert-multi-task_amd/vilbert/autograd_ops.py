@@ -193,7 +193,8 @@ def _wgrad(dy, x, weights, biases_present, need_w, need_b, launcher=None):
 class LinearFn(Function):
     """y = dropout(act(x @ cat(W).T + cat(b)), p) (+ residual). Inputs: x, residual, act, nseg, drop_p, pad_cols, out_f32,
     W..., b... pad_cols (fp32 x): see ops.linear_fwd. out_f32 (bf16 x): y is fp32 (the image-feature projection in front of
-    the fp32 embedding kernel). A bf16 x comes without act (functional.linear runs such a linear on the fp32 kernels).
+    the fp32 embedding kernel, the poolers). A bf16 x comes without act, with GELU and a bf16 result, or with ReLU and an
+    fp32 result (functional.linear runs every other such linear on the fp32 kernels).
     The dropout mask is regenerated in backward from the saved seed (vb_dropout on the incoming gradient)."""
 
     @staticmethod
@@ -201,7 +202,12 @@ class LinearFn(Function):
         weights, biases = list(wb[:nseg]), list(wb[nseg:])
         seed = next_seed() if drop_p > 0.0 else 0
         if x.dtype == BF16:
-            y, pre = ops16.linear_fwd(x, weights, biases, act, residual, drop_p=drop_p, seed=seed, out_f32=out_f32)
+            # with an activation (functional.linear: GELU with a bf16 result, ReLU with an fp32 one - the prediction-head
+            # transforms and the poolers): GELU saves gelu'(pre-activation) as FFNFn does, ReLU is masked by its output
+            y, pre = ops16.linear_fwd(x, weights, biases, act, residual, drop_p=drop_p, seed=seed, out_f32=out_f32,
+                                      want_act_grad=act == "gelu")
+            if act == "relu":
+                pre = y
         else:
             y, pre = ops.linear_fwd(x, weights, biases, act, residual, want_preact=act is not None, drop_p=drop_p,
                                     seed=seed, pad_cols=pad_cols)
@@ -220,14 +226,22 @@ class LinearFn(Function):
         biases = [rest.pop(0) if h else None for h in ctx.has_bias]
         seg_n, K = weights[0].shape[0], weights[0].shape[1]
         if dy.dtype != x.dtype:      # out_f32: the gradient of the fp32 output arrives in fp32
-            dy = ops16.cast_bf16(dy)
+            if ctx.act == "relu":    # (the poolers) mask and rounding in one pass
+                dy, pre = ops16.relu_bwd(dy, pre), None
+            else:
+                dy = ops16.cast_bf16(dy)
         elif x.dtype == BF16 or not (ops._row_strided(dy) and ctx.drop[0] == 0.0 and ctx.act is None
                                      and not ctx.needs_input_grad[1]):
             dy = dy.contiguous()     # (a row-strided gradient of padded fp32 logits feeds the GEMMs in place)
         dres = dy if ctx.needs_input_grad[1] else None
         if ctx.drop[0] > 0.0:
             dy = _dropped(dy, ctx.drop)
-        dpre = ops.act_bwd(dy, pre, ctx.act) if ctx.act is not None else dy
+        if ctx.act is None or pre is None:
+            dpre = dy
+        elif x.dtype == BF16:        # GELU: pre is the saved derivative
+            dpre = ops16.mul(dy.contiguous(), pre)
+        else:
+            dpre = ops.act_bwd(dy, pre, ctx.act)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = _dgrad(dpre, weights, K).view(x.shape)
@@ -244,6 +258,65 @@ class LinearFn(Function):
                     ops16.linear_bwd_weight_ragged(dy_, x_, want_b, dw_out, db_out)
             dws, dbs = _wgrad(dpre, x, weights, biases, need_w, need_b, launcher)
         return (dx, dres, None, None, None, None, None) + tuple(dws) + tuple(dbs)
+
+
+class RaggedLinearFn(Function):
+    """y = x @ W.T + b for a bf16 x and a weight whose height n is no tile multiple (the tied 30,522-wide MLM decoder, the
+    1,601-wide region decoder): the bf16 kernels on the zero-padded shadow (ops16.linear_ragged_*). y is an fp32 [rows, n] view
+    of a [rows, n_pad] buffer. The output carries `_vb_ragged`: a loss node that reads it directly (CrossEntropyFn, KLDivFn)
+    then hands over its gradient as the padded bf16 operands G (and G^T) these GEMMs take - a NaN placeholder travels through
+    autograd in their place (`_vb_grad16`). Any other gradient arrives in fp32 and is rounded here."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        y = ops16.linear_ragged_fwd(x, weight, bias)
+        ctx.save_for_backward(x, weight, *([bias] if bias is not None else []))
+        y._vb_ragged = True
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors[:2]
+        bias = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        n, K = weight.shape
+        rows = x.numel() // K
+        n_pad = ops16.padded(n)
+        tag = getattr(dy, "_vb_grad16", None)
+        part = None
+        if tag is not None and tag[0].shape == (rows, n_pad):
+            G, GT, part = tag       # part: fp32 column sums of the unrounded loss gradient per 64 rows (cross entropy), or None
+        else:
+            dy2 = dy.reshape(rows, n)
+            if dy2.stride(1) != 1 or dy2.stride(0) % 4 != 0 or dy2.data_ptr() % 16 != 0:
+                dy2 = dy2.contiguous() if n % 4 == 0 else torch.nn.functional.pad(dy2, (0, 4 - n % 4))[:, :n]
+            G, GT = torch.empty(rows, n_pad, dtype=BF16, device=dy.device), None
+            N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), rows, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
+                                                  G.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops16.linear_ragged_bwd_input(G, GT, weight, bias, rows).view(x.shape)
+        need_w = bool(ctx.needs_input_grad[1])
+        need_b = bool(bias is not None and ctx.needs_input_grad[2])
+        if need_b and part is not None:
+            # the bias gradient in fp32 from the loss kernel's partial sums, not from the bf16-rounded G: the column sum of the
+            # 30,522-wide decoder hardly depends on the logits, so the rounding of its ~rows terms would be its whole error
+            cb = _Claims([bias], [True])
+            db = cb.out(0, ops16.colsum_parts(part, n, cb.views()[0]))
+            need_b = False
+        if need_w or need_b:
+            launcher = lambda dy_, x_, nseg_, seg_n_, want_b, dw_out=None, db_out=None: \
+                ops16.linear_ragged_bwd_weight(dy_, x_, seg_n_, want_b, dw_out, db_out)
+            (dw,), (db_w,) = _wgrad(G, x, [weight], [bias], [need_w], [need_b], launcher)
+            db = db_w if need_b else db
+        return dx, dw, db
+
+
+def _grad16_placeholder(like, payload):
+    """What a loss node returns to autograd in place of the fp32 gradient it did not compute: a [rows, n] fp32 view of ONE
+    NaN (should anything but the ragged linear in front read it, the NaN shows) that carries the bf16 operands."""
+    p = torch.full((1, 1), float("nan"), dtype=torch.float32, device=like.device).expand(like.shape)
+    p._vb_grad16 = payload
+    return p
 
 
 class FFNFn(Function):
@@ -496,11 +569,16 @@ class CrossEntropyFn(torch.autograd.Function):
         loss, lse, count = ops.xent_fwd(logits, labels, ignore_index)
         ctx.save_for_backward(logits, labels, lse, count)
         ctx.ignore_index = ignore_index
+        ctx.to16 = bool(getattr(logits, "_vb_ragged", False))      # the logits of a RaggedLinearFn, read here directly
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         logits, labels, lse, count = ctx.saved_tensors
+        if ctx.to16:
+            want_t = ops16.padded(logits.shape[1]) >= ops16.WGRAD_FORM_MIN_WIDTH
+            return _grad16_placeholder(logits, ops16.xent_bwd16(grad_loss, logits, labels, ctx.ignore_index, lse, count,
+                                                                want_t, want_colsum=True)), None, None
         return ops.xent_bwd(grad_loss, logits, labels, ctx.ignore_index, lse, count), None, None
 
 
@@ -512,11 +590,15 @@ class KLDivFn(torch.autograd.Function):
         loss, lse, tsum = ops.kl_fwd(scores, target, divisor)
         ctx.save_for_backward(scores, target, lse, tsum)
         ctx.divisor = divisor
+        ctx.to16 = bool(getattr(scores, "_vb_ragged", False))
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         scores, target, lse, tsum = ctx.saved_tensors
+        if ctx.to16:
+            return _grad16_placeholder(scores, (ops16.kl_bwd16(grad_loss, scores, target, lse, tsum, ctx.divisor), None, None)), \
+                None, None
         return ops.kl_bwd(grad_loss, scores, target, lse, tsum, ctx.divisor), None, None
 
 
@@ -556,6 +638,23 @@ class NCERegionFn(torch.autograd.Function):
     def backward(ctx, grad_loss):
         dsave, count = ctx.saved_tensors
         return (ops.nce_bwd(grad_loss, dsave, ctx.valid, count),) + (None,) * 9
+
+
+class GatherRows16Fn(Function):
+    """compact[r] = src[row_map[r]] on bf16 rows (vilbert.py `_row_map`: the rows of an encoder output the poolers and a
+    prediction head read; -1 = a zero padding row). Backward: ONE scatter of the compact gradient into the bf16 gradient of
+    the whole [rows, H] tensor - every row written once, zeros where no compact row stands for it."""
+
+    @staticmethod
+    def forward(ctx, src, row_map):
+        ctx.save_for_backward(row_map)
+        ctx.full_rows = src.shape[0]
+        return ops16.gather_rows(src, row_map)
+
+    @staticmethod
+    def backward(ctx, d):
+        (row_map,) = ctx.saved_tensors
+        return ops16.scatter_rows(d.contiguous(), row_map, ctx.full_rows), None
 
 
 class CastFn(Function):

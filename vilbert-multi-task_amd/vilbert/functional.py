@@ -40,6 +40,11 @@ def to_f32(x):
     return A.CastFn.apply(x, False) if _needs_grad(x) else ops16.cast_f32(x)
 
 
+def gather_rows16(src, row_map):
+    """bf16 [M, H] = src[row_map] (src bf16 [rows, H], row_map int32 [M], -1 = zero row); backward scatters once."""
+    return A.GatherRows16Fn.apply(src, row_map) if _needs_grad(src) else ops16.gather_rows(src, row_map)
+
+
 def _uniform_bias(biases):
     return all(b is None for b in biases) or all(b is not None for b in biases)
 
@@ -57,9 +62,21 @@ def linear(x, weights, biases=None, act=None, residual=None, drop_p=0.0, pad_col
     kern = ops
     if _is16(x):
         seg_n, K = weights[0].shape
-        ok = (ops16.eligible(K, len(weights) * seg_n, seg_n, act) and x.is_cuda and _uniform_bias(biases)
-              and (residual is None or residual.dtype == BF16))
-        if not ok or (grad and act is not None):
+        base = x.is_cuda and _uniform_bias(biases) and (residual is None or residual.dtype == BF16)
+        ok = base and ops16.eligible(K, len(weights) * seg_n, seg_n, act)
+        if (not ok and base and out_f32 and len(weights) == 1 and act is None and residual is None and drop_p == 0.0
+                and ops16.ragged_ok(K, seg_n)):
+            # an output width that is no tile multiple (the 30,522-wide MLM decoder, the 1,601-wide region decoder): the bf16
+            # kernels on a zero-padded shadow, fp32 result
+            if grad:
+                return A.RaggedLinearFn.apply(x, weights[0], biases[0])
+            return ops16.linear_ragged_fwd(x, weights[0], biases[0])
+        # under autograd an activation stays on the bf16 kernels where its backward has one: GELU with a bf16 result (the
+        # saved derivative is multiplied in), ReLU with an fp32 result (masked by the output); swish, and VB_BF16_HEADS=0,
+        # take the fp32 kernels
+        act16 = (ops16.heads_enabled() and residual is None and drop_p == 0.0
+                 and ((act == "gelu" and not out_f32) or (act == "relu" and out_f32)))
+        if not ok or (grad and act is not None and not act16):
             y = linear(to_f32(x), weights, biases, act, to_f32(residual), drop_p)
             return y if out_f32 else to_bf16(y)
         kern = ops16

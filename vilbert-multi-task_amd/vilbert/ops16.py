@@ -129,6 +129,7 @@ shadows = _SHADOWS.get
 def shadow_cache_clear():
     _SHADOWS.clear()
     _TABLES.clear()
+    _RAGGED.clear()
 
 
 def refresh_stale(device):
@@ -136,11 +137,10 @@ def refresh_stale(device):
     epoch moved since the shadows of `device` were refreshed - an optimizer stepped - refresh all of them now, with the one
     launch over the device table (built here, eagerly, so that it never is built inside a stream capture or a branch)."""
     t = _TABLES.get(device.index)
-    if t is not None and t.get("epoch") == _WEIGHTS_EPOCH[0]:
-        return
-    if _SHADOWS.entries(device):
+    if not (t is not None and t.get("epoch") == _WEIGHTS_EPOCH[0]) and _SHADOWS.entries(device):
         with torch.no_grad():
             _refresh_all(device)
+    _refresh_ragged(device)      # (the zero-padded shadows of the heads: one launch each, none when nothing is stale)
 
 
 def _rows2(x, K):
@@ -279,6 +279,267 @@ def linear_bwd_weight_ragged(dy, x, want_bias, dw_out=None, db_out=None):
                2.0 * M * n * K, ("wgrad16", M, n, K, 1))
     # (on a weight-gradient side stream the caller has made that stream torch's current one: the two bf16 temporaries come
     # from its allocator pool)
+    return dws, dbs
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Poolers, prediction heads and losses on the bf16 stream (csrc/heads16.hip, include/vilbert_hip_heads.h): the row kernels
+# and the linear whose output width is no tile multiple (the tied 30,522-wide MLM decoder, the 1,601-wide region decoder).
+# VB_BF16_HEADS=0 keeps them on the fp32-tensor kernels between two casts, as before.
+# ---------------------------------------------------------------------------------------------------------------
+_HEADS = {"on": os.environ.get("VB_BF16_HEADS", "1") != "0"}
+# Widths from which the input gradient of a ragged linear runs in weight-gradient form (linear_ragged_bwd_input): a long
+# contraction into few output tiles leaves most of the chip idle in one persistent forward-kernel launch, the weight-gradient
+# kernel splits it. Below, the forward kernel on the transposed shadow. (tools/bf16_heads_bench.py times both forms.)
+WGRAD_FORM_MIN_WIDTH = int(os.environ.get("VB_BF16_HEADS_WGRAD_FORM", "8192"))
+
+
+def heads_enabled():
+    return _HEADS["on"]
+
+
+def set_heads(on):
+    prev, _HEADS["on"] = _HEADS["on"], bool(on)
+    return prev
+
+
+def padded(n):
+    """256 * ceil(n / 256) (vbh_padded)."""
+    return (n + 255) // 256 * 256
+
+
+def ragged_ok(K, n_out):
+    """A linear of any width n_out >= 1 that the padded bf16 kernels serve (linear_ragged_*)."""
+    return _HEADS["on"] and K % 128 == 0 and n_out >= 1 and n_out % 256 != 0
+
+
+def _rows16(t, what):
+    """(2-D row-strided bf16 view, row stride) of a [..., cols] tensor the row kernels take; copies only if it has to."""
+    if not (t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.stride(0) % 8 == 0
+            and t.data_ptr() % 16 == 0):
+        t = ops._contig(t).view(-1, t.shape[-1])
+    dev_bf16(t, what)
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def gather_rows(src, row_map):
+    """out[r] = src[row_map[r]] (bf16 [M, cols]); src bf16 [rows, cols] (row-strided view allowed), row_map int32 [M]: an entry
+    outside [0, rows) (-1 = padding) gives a zero row."""
+    src2, lds = _rows16(src, "gather source")
+    if row_map.dtype != torch.int32 or not row_map.is_contiguous() or not row_map.is_cuda:
+        raise RuntimeError("gather_rows: expected a contiguous int32 row map on a HIP device")
+    M, cols = row_map.numel(), src2.shape[1]
+    out = torch.empty(M, cols, dtype=BF16, device=src.device)
+    N.check(N.lib().vbh_gather_rows_bf16(N.stream_ptr(), M, cols, src2.data_ptr(), lds, src2.shape[0], row_map.data_ptr(),
+                                         out.data_ptr(), cols), "vbh_gather_rows_bf16")
+    return out
+
+
+def scatter_rows(compact, row_map, full_rows):
+    """full[R] = compact[r] for the first r with row_map[r] == R, zeros elsewhere (bf16 [full_rows, cols]): the adjoint of
+    gather_rows for a map that names every row once. Two launches (invert the map, write every row of `full` once)."""
+    c2, ldc = _rows16(compact, "scatter source")
+    M, cols = c2.shape
+    if row_map.dtype != torch.int32 or not row_map.is_contiguous() or row_map.numel() != M:
+        raise RuntimeError("scatter_rows: expected a contiguous int32 row map with one entry per compact row")
+    inv = torch.empty(full_rows, dtype=torch.int32, device=compact.device)
+    full = torch.empty(full_rows, cols, dtype=BF16, device=compact.device)
+    N.check(N.lib().vbh_invert_map(N.stream_ptr(), full_rows, M, row_map.data_ptr(), inv.data_ptr()), "vbh_invert_map")
+    N.check(N.lib().vbh_scatter_rows_bf16(N.stream_ptr(), full_rows, cols, c2.data_ptr(), ldc, M, inv.data_ptr(),
+                                          full.data_ptr(), cols), "vbh_scatter_rows_bf16")
+    return full
+
+
+def relu_bwd(dy, y):
+    """bf16(dy * (y > 0)) from the fp32 gradient and the fp32 OUTPUT of a ReLU (the poolers)."""
+    dy, y = ops._contig(dy), ops._contig(y)
+    rows, cols = ops._rows(y)
+    out = torch.empty(y.shape, dtype=BF16, device=y.device)
+    N.check(N.lib().vbh_relu_bwd_bf16(N.stream_ptr(), rows, cols, N.dev_f32(dy, "relu grad_output"), cols,
+                                      N.dev_f32(y, "relu output"), cols, out.data_ptr(), cols), "vbh_relu_bwd_bf16")
+    return out
+
+
+def mul(a, b):
+    """bf16(a * b) of two bf16 tensors of one shape (a gradient times the saved gelu')."""
+    a, b = ops._contig(a), ops._contig(b)
+    rows, cols = ops._rows(a)
+    out = torch.empty_like(a)
+    N.check(N.lib().vbh_mul_bf16(N.stream_ptr(), rows, cols, dev_bf16(a, "mul input"), cols, dev_bf16(b, "mul input"), cols,
+                                 out.data_ptr(), cols), "vbh_mul_bf16")
+    return out
+
+
+def xent_bwd16(grad_loss, logits, labels, ignore_index, lse, count, want_t, want_colsum=False):
+    """The cross-entropy gradient as the bf16 operands of the GEMMs in front: (G [rows, n_pad], GT [n_pad, m_pad] or None),
+    pad columns / rows exact zeros. logits fp32 [rows, n] (row-strided view allowed). want_colsum: a third value, fp32
+    [ceil(rows / 64), n_pad] column sums of the UNROUNDED gradient per 64 rows (colsum_parts adds them up: the bias gradient
+    of the decoder in front, in fp32 as the fp32-tensor path computes it)."""
+    if not ops._row_strided(logits):
+        logits = ops._contig(logits)
+    labels = ops._contig(labels)
+    rows, n = logits.shape
+    ld = logits.stride(0) if rows > 1 else max(n, logits.stride(0))
+    n_pad, m_pad = padded(n), padded(rows)
+    grad_loss = ops._contig(grad_loss).reshape(1)
+    G = torch.empty(rows, n_pad, dtype=BF16, device=logits.device)
+    GT = torch.empty(n_pad, m_pad, dtype=BF16, device=logits.device) if want_t else None
+    part = torch.empty((rows + 63) // 64, n_pad, dtype=torch.float32, device=logits.device) if want_colsum else None
+    N.check(N.lib().vbh_xent_bwd_bf16(
+        N.stream_ptr(), rows, n, N.dev_f32(logits, "cross_entropy logits"), ld, N.dev_i64(labels, "cross_entropy labels"),
+        ignore_index, N.dev_f32(lse, "cross_entropy lse"), N.dev_f32(grad_loss, "cross_entropy grad"),
+        N.dev_f32(count, "cross_entropy count"), G.data_ptr(), n_pad, GT.data_ptr() if want_t else None, m_pad,
+        part.data_ptr() if want_colsum else None), "vbh_xent_bwd_bf16")
+    return (G, GT, part) if want_colsum else (G, GT)
+
+
+def colsum_parts(part, n, out=None):
+    """out[j] += sum over the rows of `part` (fp32 [parts, ld >= n]) in row order, j < n; out: fp32 [n] target (a gradient-arena
+    slice) or None = a zero-filled tensor allocated here. Returns out."""
+    if out is None:
+        out = torch.zeros(n, dtype=torch.float32, device=part.device)
+    N.check(N.lib().vbh_colsum_parts(N.stream_ptr(), part.shape[0], n, N.dev_f32(part, "column-sum partials"), part.stride(0),
+                                     N.dev_f32(out, "bias gradient")), "vbh_colsum_parts")
+    return out
+
+
+def kl_bwd16(grad_loss, scores, target, lse, tsum, divisor):
+    """The KL gradient as bf16 G [rows, n_pad] (pad columns zero); scores fp32 [rows, n] (row-strided view allowed)."""
+    if not ops._row_strided(scores):
+        scores = ops._contig(scores)
+    target = ops._contig(target)
+    rows, n = scores.shape
+    ld = scores.stride(0) if rows > 1 else max(n, scores.stride(0))
+    n_pad = padded(n)
+    grad_loss = ops._contig(grad_loss).reshape(1)
+    G = torch.empty(rows, n_pad, dtype=BF16, device=scores.device)
+    dh, dd, _keep = ops._divisor(divisor)
+    N.check(N.lib().vbh_kl_bwd_bf16(
+        N.stream_ptr(), rows, n, N.dev_f32(scores, "kl_div scores"), ld, N.dev_f32(target, "kl_div target"), n,
+        N.dev_f32(lse, "kl_div lse"), N.dev_f32(tsum, "kl_div tsum"), N.dev_f32(grad_loss, "kl_div grad"), dh, dd,
+        G.data_ptr(), n_pad), "vbh_kl_bwd_bf16")
+    return G
+
+
+def _ragged_build(weights, biases, _hint):
+    """{w16 [n_pad, K], wt16 [K, n_pad], bias [n_pad] fp32}: the zero-padded bf16 shadow of ONE fp32 weight [n, K] and bias."""
+    w = weights[0]
+    n, K = w.shape
+    if len(weights) != 1 or not w.is_contiguous() or K % 64 != 0:
+        raise RuntimeError("linear (bf16, ragged width): one contiguous weight with K % 64 == 0 expected")
+    n_pad = padded(n)
+    pay = {"w16": torch.empty(n_pad, K, dtype=BF16, device=w.device), "wt16": torch.empty(K, n_pad, dtype=BF16, device=w.device),
+           "bias": torch.empty(n_pad, dtype=torch.float32, device=w.device), "bref": None}
+    _ragged_refresh(pay, weights, biases)
+    return pay
+
+
+def _ragged_refresh(pay, weights, biases):
+    import weakref
+    w = weights[0]
+    b = biases[0] if biases else None
+    n, K = w.shape
+    pay["bref"] = weakref.ref(b) if b is not None else None
+    N.check(N.lib().vbh_weight_shadow_ragged(
+        N.stream_ptr(), n, K, N.dev_f32(w.detach(), "linear weight"), K,
+        N.dev_f32(ops._contig(b.detach()), "linear bias") if b is not None else None, pay["w16"].data_ptr(),
+        pay["wt16"].data_ptr(), pay["bias"].data_ptr()), "vbh_weight_shadow_ragged")
+
+
+# the padded shadows: keyed like _SHADOWS; vb_weight_shadow_multi walks whole 64-row tiles of its sources, so these are not in
+# its table - refresh_stale() refreshes each stale one with its own launch
+_RAGGED = DerivedWeights(_ragged_build, _ragged_refresh, bias_versions=True)
+
+
+def ragged_shadows(weight, bias):
+    return _RAGGED.get([weight], [bias])
+
+
+def _refresh_ragged(device):
+    epoch = _WEIGHTS_EPOCH[0]
+    for _k, e in _RAGGED.entries(device):
+        if e.epoch == epoch or not e.alive():
+            continue
+        w = e.wrefs[0]()
+        bref = e.payload["bref"]
+        b = bref() if bref is not None else None
+        if bref is not None and b is None:
+            continue
+        with torch.no_grad():
+            _ragged_refresh(e.payload, [w], [b])
+        e.vers, e.epoch = _RAGGED._versions([w], [b]), epoch
+
+
+def linear_ragged_fwd(x, weight, bias):
+    """x @ weight.T + bias for a weight [n, K] of any height n: vb_linear_bf16 on the zero-padded shadow, fp32 result in a
+    [rows, n_pad] buffer; returns its [..., n] view (row stride n_pad: 16-byte aligned rows for the loss kernels)."""
+    n, K = weight.shape
+    pay = ragged_shadows(weight, bias)
+    n_pad = pay["w16"].shape[0]
+    x2, lead = _rows2(x, K)
+    M = x2.shape[0]
+    y = torch.empty(M, n_pad, dtype=torch.float32, device=x.device)
+    a = N.LinearBf16Args()
+    a.A, a.lda, a.W, a.ldw = dev_bf16(x2, "linear input"), K, pay["w16"].data_ptr(), K
+    if bias is not None:
+        a.bias[0] = pay["bias"].data_ptr()
+    a.C32, a.ldc32 = y.data_ptr(), n_pad
+    a.M, a.N, a.K = M, n_pad, K
+    if M:
+        ops._timed(lambda: N.check(N.lib().vb_linear_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_linear_bf16 (ragged)"),
+                   2.0 * M * n_pad * K, ("fwd16", M, n_pad, K, 1))
+    y = y[:, :n]
+    return y if len(lead) == 1 else y.reshape(lead + (n,))
+
+
+def linear_ragged_bwd_input(G, GT, weight, bias, rows, form=None):
+    """dX bf16 [rows, K] = G[:, :n] @ weight from the padded bf16 gradient G [rows, n_pad] (GT [n_pad, m_pad] = its transpose,
+    or None). form "dgrad": the forward kernel on the transposed padded shadow. form "wgrad" (needs GT): the weight-gradient
+    kernel, dX = GT^T w16 accumulated in fp32 into a zero-filled buffer - its contraction splits and, in the deterministic
+    setting, the ordered reduce come from the planner - then one cast. Default: "wgrad" from WGRAD_FORM_MIN_WIDTH columns."""
+    n, K = weight.shape
+    pay = ragged_shadows(weight, bias)
+    n_pad = pay["w16"].shape[0]
+    if form is None:
+        form = "wgrad" if GT is not None and n_pad >= WGRAD_FORM_MIN_WIDTH else "dgrad"
+    if form == "wgrad":
+        N.ensure_deterministic(G.device)
+        m_pad = GT.shape[1]
+        dx32 = torch.zeros(rows, K, dtype=torch.float32, device=G.device)
+        a = N.WgradBf16Args()
+        a.dY, a.ldy, a.X, a.ldx = dev_bf16(GT, "linear grad_output (transposed)"), m_pad, pay["w16"].data_ptr(), K
+        a.M, a.K, a.nseg, a.seg_n, a.ldw, a.n_valid = n_pad, K, 1, m_pad, K, rows
+        a.dW[0] = dx32.data_ptr()
+        ops._timed(lambda: N.check(N.lib().vb_wgrad_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_wgrad_bf16 (input gradient)"),
+                   2.0 * rows * n_pad * K, ("dgrad16w", rows, n_pad, K, 1))
+        return cast_bf16(dx32)
+    dx = torch.empty(rows, K, dtype=BF16, device=G.device)
+    a = N.LinearBf16Args()
+    a.A, a.lda, a.W, a.ldw = dev_bf16(G, "linear grad_output"), n_pad, pay["wt16"].data_ptr(), n_pad
+    a.C, a.ldc = dx.data_ptr(), K
+    a.M, a.N, a.K = rows, K, n_pad
+    ops._timed(lambda: N.check(N.lib().vb_linear_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_linear_bf16 (dgrad, ragged)"),
+               2.0 * rows * n_pad * K, ("dgrad16", rows, n_pad, K, 1))
+    return dx
+
+
+def linear_ragged_bwd_weight(G, x, n, want_bias, dw_out=None, db_out=None):
+    """dW [n, K] += G[:, :n]^T x, db [n] += colsum(G[:, :n]) straight from the padded bf16 gradient G [rows, n_pad]: one
+    vb_wgrad_bf16 launch that writes rows < n only. Same contract as linear_bwd_weight (nseg = 1)."""
+    N.ensure_deterministic(G.device)
+    K = x.shape[-1]
+    x2, _ = _rows2(x, K)
+    M, n_pad = G.shape
+    if x2.shape[0] != M:
+        raise RuntimeError("linear_bwd_weight: row count mismatch")
+    dws, dbs = ops.wgrad_targets(1, n, K, want_bias, dw_out, db_out, G.device)
+    a = N.WgradBf16Args()
+    a.dY, a.ldy, a.X, a.ldx = dev_bf16(G, "linear grad_output"), n_pad, dev_bf16(x2, "linear input"), K
+    a.M, a.K, a.nseg, a.seg_n, a.ldw, a.n_valid = M, K, 1, n_pad, K, n
+    a.dW[0] = N.dev_f32(dws[0], "weight gradient")
+    a.dbias[0] = N.dev_f32(dbs[0], "bias gradient") if dbs[0] is not None else None
+    ops._timed(lambda: N.check(N.lib().vb_wgrad_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_wgrad_bf16 (ragged)"),
+               2.0 * M * n * K, ("wgrad16", M, n, K, 1))
     return dws, dbs
 
 

@@ -984,6 +984,10 @@ class BertModel(BertPreTrainedModel):
                 image_attention_mask=None, co_attention_mask=None, task_ids=None,
                 output_all_encoded_layers=False, output_all_attention_masks=False):
         from . import ops
+        # `_bf16_seq_out` (internal, left on the module by BertForMultiModalPreTraining for this one call - the way the encoder's
+        # `_last_layer_rows` is handed over): where the encoder ran on the bf16 stream, return its bf16 sequence outputs
+        # as they are - no fp32 casts, no pooling (pooled outputs None): that caller pools and predicts on gathered rows
+        bf16_seq_out = self.__dict__.pop("_bf16_seq_out", False)
         if attention_mask is None:
             attention_mask = torch.ones_like(input_txt)
         if token_type_ids is None:
@@ -1027,6 +1031,10 @@ class BertModel(BertPreTrainedModel):
             output_all_encoded_layers=output_all_encoded_layers,
             output_all_attention_masks=output_all_attention_masks)
 
+        if (bf16_seq_out and not output_all_encoded_layers and _native.bf16_stream()
+                and encoded_layers_t[-1].dtype == torch.bfloat16 and encoded_layers_v[-1].dtype == torch.bfloat16
+                and encoded_layers_t[-1].dim() == 3):
+            return encoded_layers_t[-1], encoded_layers_v[-1], None, None, all_attention_mask
         # bf16 mode / MX inference mode: the encoder keeps its residual stream in bf16; the callers (poolers, heads, users)
         # get fp32
         encoded_layers_t = [F.to_f32(t) for t in encoded_layers_t]
@@ -1106,12 +1114,30 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         encoder = self.bert.encoder
         if last_layer_rows is not None:
             encoder.__dict__["_last_layer_rows"] = last_layer_rows
+        # bf16 mode, training step: poolers, prediction heads and losses stay on the bf16 stream (_losses_on_the_bf16_stream):
+        # the encoder's bf16 outputs come back as they are, without the fp32 casts of the two full hidden states. (As with the
+        # row maps above, an evaluation pass with labels keeps the path it had.)
+        if (native_losses and image_label is not None and not output_all_attention_masks and _native.bf16_stream()
+                and self.training and torch.is_grad_enabled() and input_ids.is_cuda and image_feat.is_cuda
+                and self._bf16_heads_ok()):
+            self.bert.__dict__["_bf16_seq_out"] = True
         try:
             sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
                 input_ids, image_feat, image_loc, token_type_ids, attention_mask, image_attention_mask,
                 output_all_encoded_layers=False, output_all_attention_masks=output_all_attention_masks)
         finally:
             encoder.__dict__.pop("_last_layer_rows", None)
+            self.bert.__dict__.pop("_bf16_seq_out", None)
+        if pooled_output_t is None:
+            # the encoder ran in bf16 and handed its outputs over uncast
+            losses = self._losses_on_the_bf16_stream(sequence_output_t, sequence_output_v, masked_lm_labels, image_label,
+                                                     image_target, next_sentence_label)
+            if losses is not None:
+                return losses
+            # nothing labelled (exact gather): the reference-shaped path below, on what BertModel returns otherwise
+            sequence_output_t, sequence_output_v = F.to_f32(sequence_output_t), F.to_f32(sequence_output_v)
+            pooled_output_t = self.bert.t_pooler(sequence_output_t)
+            pooled_output_v = self.bert.v_pooler(sequence_output_v)
         if native_losses:
             losses = self._losses_at_labelled_positions(sequence_output_t, sequence_output_v, pooled_output_t,
                                                         pooled_output_v, masked_lm_labels, image_label,
@@ -1140,6 +1166,90 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
                                          masked_lm_labels.reshape(-1), ignore_index=-1)
         next_sentence_loss = F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1),
                                              ignore_index=-1)
+        return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
+
+    def _bf16_heads_ok(self):
+        """Every pooler / head width passes the shape rules of the bf16 kernels (ops16.eligible: K % 128, widths % 256; the bf16
+        LayerNorm: <= 1024 columns; the decoders: any width through the zero-padded shadow) and VB_BF16_HEADS is not 0."""
+        from . import ops16
+        c = self.config
+        H, Hv, Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
+
+        def out_ok(K, n):
+            return ops16.eligible(K, n) or ops16.ragged_ok(K, n)
+        return (ops16.heads_enabled() and ops16.eligible(H, Hb, act="relu") and ops16.eligible(Hv, Hb, act="relu")
+                and ops16.eligible(H, H) and ops16.eligible(Hv, Hv) and H <= 1024 and Hv <= 1024
+                and out_ok(H, self.cls.predictions.decoder.weight.size(0)) and out_ok(Hv, c.v_target_size))
+
+    def _losses_on_the_bf16_stream(self, sequence_output_t, sequence_output_v, masked_lm_labels, image_label, image_target,
+                                   next_sentence_label):
+        """_losses_at_labelled_positions for the bf16 mode: sequence outputs bf16 [B, T, H] / [B, R, Hv] straight from the encoder.
+        Per stream ONE gather of the rows anything behind the encoder reads - _row_map: row 0 of every sample (the poolers),
+        then the labelled rows, every row once - into compact bf16 [rows, H]; the poolers (ReLU, fp32 result) run on its first
+        B rows, the prediction heads (dense + GELU, LayerNorm, decoder) on _row_map's head indices, all on the bf16 kernels;
+        the decoders' logits are fp32 and the losses hand their gradient back in bf16 (autograd_ops.RaggedLinearFn). Backward
+        scatters the compact gradient once per stream into the bf16 gradient of the encoder output. The pooled outputs and
+        everything behind them (alignment head and loss) stay fp32. Returns None when nothing is labelled (exact gather)."""
+        cls = self.cls
+        batch, n_tok, n_reg_all = sequence_output_t.size(0), sequence_output_t.size(1), sequence_output_v.size(1)
+        lm_flat = masked_lm_labels.reshape(-1)
+        labelled = image_label == 1
+        per = labelled.reshape(labelled.size(0), -1).size(1)        # regions without the global row 0
+        static = self._static_gather()
+        if not static and self.label_capacity == "auto" and self._auto_capacity is None:
+            frac = max(float((lm_flat != -1).sum()) / max(lm_flat.numel(), 1), float(labelled.sum()) / max(labelled.numel(), 1))
+            self._auto_capacity = min(1.0, 1.2 * frac + 0.01)
+        if static:
+            idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r = self._static_label_rows(masked_lm_labels, image_label)
+        else:
+            idx_t = torch.nonzero(lm_flat != -1).squeeze(1)
+            idx_r = torch.nonzero(labelled.reshape(-1)).squeeze(1)      # index into [B, n_reg_all - 1]
+            if idx_t.numel() == 0 or idx_r.numel() == 0:
+                return None
+            labels_t = lm_flat.index_select(0, idx_t)
+            valid_r, divisor_r = None, float(idx_r.numel())
+            n_t, n_r = idx_t.numel(), idx_r.numel()
+        idx_v = idx_r + torch.div(idx_r, per, rounding_mode="floor") + 1   # same rows inside [B, n_reg_all]
+        map_t, head_t = _row_map(idx_t, n_t, batch, n_tok)
+        map_v, head_v = _row_map(idx_v, n_r, batch, n_reg_all)
+        compact_t = F.gather_rows16(sequence_output_t.reshape(batch * n_tok, -1), map_t)
+        compact_v = F.gather_rows16(sequence_output_v.reshape(batch * n_reg_all, -1), map_v)
+
+        t_pool, v_pool = self.bert.t_pooler.dense, self.bert.v_pooler.dense
+        pooled_output_t = F.linear(compact_t[:batch], t_pool.weight, t_pool.bias, act="relu", out_f32=True)
+        pooled_output_v = F.linear(compact_v[:batch], v_pool.weight, v_pool.bias, act="relu", out_f32=True)
+        pooled_output = _dropout(_fuse_pooled(cls.fusion_method, pooled_output_t, pooled_output_v), cls.dropout)
+        seq_relationship_score = F.linear(pooled_output, cls.bi_seq_relationship.weight, cls.bi_seq_relationship.bias)
+        next_sentence_loss = F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1),
+                                             ignore_index=-1)
+
+        pred = cls.predictions
+        logits_t = F.linear(pred.transform(compact_t.index_select(0, head_t)), pred.decoder.weight, pred.bias, out_f32=True)
+        masked_lm_loss = F.cross_entropy(logits_t, labels_t, ignore_index=-1)
+
+        img = cls.imagePredictions
+        scores_v = F.linear(img.transform(compact_v.index_select(0, head_v)), img.decoder.weight, img.decoder.bias,
+                            out_f32=True)
+        if self.visual_target == 2:
+            count = divisor_r if torch.is_tensor(divisor_r) else torch.full((1,), divisor_r, dtype=torch.float32,
+                                                                          device=scores_v.device)
+            self._nce_seed = A.next_seed()
+            masked_img_loss = F.nce_region_loss(ops._contig(scores_v), image_target, idx_r, valid_r, count, image_target.size(0),
+                                                per, int(self.num_negative * 0.7), int(self.num_negative * 0.3),
+                                                seed=self._nce_seed)
+            return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
+        target = image_target.reshape(-1, image_target.size(-1)).index_select(0, idx_r)
+        if valid_r is not None:
+            target = target * valid_r.unsqueeze(1).to(target.dtype)     # padding rows: all-zero target
+        if self.visual_target == 1:
+            if valid_r is not None:
+                sq = self.vis_criterion(scores_v, target) * valid_r.unsqueeze(1).to(scores_v.dtype)
+                masked_img_loss = torch.sum(sq) / torch.clamp(divisor_r * float(image_target.size(-1)), min=1.0).squeeze(0)
+            else:
+                masked_img_loss = torch.sum(self.vis_criterion(scores_v, target)) / max(
+                    torch.sum(labelled.unsqueeze(2).expand(-1, -1, image_target.size(-1))), 1)
+        else:
+            masked_img_loss = F.kl_div_log_softmax(scores_v, target, divisor_r)
         return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
 
     def _static_gather(self):
