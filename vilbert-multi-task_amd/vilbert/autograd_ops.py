@@ -641,7 +641,7 @@ class NCERegionFn(torch.autograd.Function):
 
 
 class GatherRows16Fn(Function):
-    """compact[r] = src[row_map[r]] on bf16 rows (vilbert.py `_row_map`: the rows of an encoder output the poolers and a
+    """compact[r] = src[row_map[r]] on bf16 rows (vilbert.py `_head_row_maps` / `_row_map`: the rows of an encoder output the poolers and a
     prediction head read; -1 = a zero padding row). Backward: ONE scatter of the compact gradient into the bf16 gradient of
     the whole [rows, H] tensor - every row written once, zeros where no compact row stands for it."""
 

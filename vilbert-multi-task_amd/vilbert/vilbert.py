@@ -13,6 +13,7 @@ hand-written gfx950 kernels of libvilbert_hip.so instead of torch ops:
 registration order and ``init_weights`` behave exactly like the reference; their own ``forward`` is
 never used. There is no CPU path: calling a model on CPU tensors raises.
 """
+import collections
 import copy
 import json
 import logging
@@ -865,6 +866,24 @@ def _row_map(idx, n_valid, batch, per_sample):
     return torch.cat(parts).to(torch.int32), head
 
 
+# The labelled rows of a pre-training step (BertForMultiModalPreTraining._label_rows): idx_t / idx_r index the flat
+# [B * T] tokens / [B * (regions without the global row)] regions, labels_t holds the token labels at idx_t. Fixed-capacity
+# gather: valid_r flags the region rows in front of the padding, divisor_r (1-element fp32) and n_t / n_r are device
+# scalars. Exact gather: valid_r None, divisor_r a float, n_t / n_r host ints.
+_LabelRows = collections.namedtuple("_LabelRows", "idx_t labels_t idx_r valid_r divisor_r n_t n_r")
+
+
+def _with_global_row(idx_r, per):
+    """Rows idx_r of the flat [B, per] regions -> the same rows inside [B, per + 1], behind every sample's global row 0."""
+    return idx_r + torch.div(idx_r, per, rounding_mode="floor") + 1
+
+
+def _head_row_maps(rows, batch, n_tok, n_reg_all):
+    """_row_map of the text and of the image stream for the _LabelRows `rows` -> (map_t, head_t), (map_v, head_v)."""
+    idx_v = _with_global_row(rows.idx_r, n_reg_all - 1)
+    return _row_map(rows.idx_t, rows.n_t, batch, n_tok), _row_map(idx_v, rows.n_r, batch, n_reg_all)
+
+
 def _fuse_pooled(fusion_method, pooled_output_t, pooled_output_v):
     if fusion_method == "sum":
         return pooled_output_t + pooled_output_v
@@ -1064,10 +1083,8 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         self.apply(self.init_weights)
         self.visual_target = config.visual_target
         self.num_negative = config.num_negative
-        # None: the labelled rows are gathered exactly (one host sync per step); a fraction in (0, 1]: sync-free
-        # fixed-capacity gather of that share of the token / region positions (see _losses_at_labelled_positions)
-        # None: exact gather of the labelled rows (one host sync per step); a fraction of the positions or "auto": sync-free
-        # fixed-capacity gather (see _losses_at_labelled_positions)
+        # None: exact gather of the labelled rows (one host sync per step); a fraction in (0, 1] of the token / region
+        # positions or "auto": sync-free fixed-capacity gather (see _label_rows)
         self.label_capacity = None
         self._auto_capacity = None
         self._label_counts = None
@@ -1096,30 +1113,21 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         # host sync), and the output + feed-forward block of the last text / image layer runs on them alone (layers.py row
         # maps). Every other step - the exact gather (its torch.nonzero would stall the launch queue in front of the last
         # layer), inference, attention maps, the bf16 stream, fp8 / MX, `VB_LAST_LAYER_ROWS=0` - runs the whole layers.
-        gathered = None
+        rows = head_t = head_v = None
         native_losses = with_labels and (self.visual_target in (0, 1) or self._nce_native(image_feat, image_target))
-        if native_losses and image_label is not None and not output_all_attention_masks and self._static_gather() \
-                and self.training and torch.is_grad_enabled() and input_ids.is_cuda and layers.rows_enabled() \
-                and not _native.bf16_stream() and not _native.fp8_enabled() and not self.config.task_specific_tokens \
-                and self.bert.encoder.tail_takes_rows():
-            gathered = self._static_label_rows(masked_lm_labels, image_label)
-            batch, n_tok, n_reg_all = input_ids.size(0), input_ids.size(1), image_feat.size(1)
-            idx_t, n_t, idx_r, n_r = gathered[0], gathered[5], gathered[2], gathered[6]
-            idx_v = idx_r + torch.div(idx_r, n_reg_all - 1, rounding_mode="floor") + 1
-            map_t, head_t = _row_map(idx_t, n_t, batch, n_tok)
-            map_v, head_v = _row_map(idx_v, n_r, batch, n_reg_all)
-            last_layer_rows, gathered = (map_t, map_v), gathered + (head_t, head_v)
-        else:
-            last_layer_rows = None
+        # what both compact-row routes need: a training step with region labels on the device, no attention maps asked for
+        compact_step = (native_losses and image_label is not None and not output_all_attention_masks and self.training
+                        and torch.is_grad_enabled() and input_ids.is_cuda)
         encoder = self.bert.encoder
-        if last_layer_rows is not None:
-            encoder.__dict__["_last_layer_rows"] = last_layer_rows
+        if compact_step and self._static_gather() and layers.rows_enabled() and not _native.bf16_stream() \
+                and not _native.fp8_enabled() and not self.config.task_specific_tokens and encoder.tail_takes_rows():
+            rows = self._label_rows(masked_lm_labels, image_label)
+            (map_t, head_t), (map_v, head_v) = _head_row_maps(rows, input_ids.size(0), input_ids.size(1), image_feat.size(1))
+            encoder.__dict__["_last_layer_rows"] = (map_t, map_v)
         # bf16 mode, training step: poolers, prediction heads and losses stay on the bf16 stream (_losses_on_the_bf16_stream):
         # the encoder's bf16 outputs come back as they are, without the fp32 casts of the two full hidden states. (As with the
         # row maps above, an evaluation pass with labels keeps the path it had.)
-        if (native_losses and image_label is not None and not output_all_attention_masks and _native.bf16_stream()
-                and self.training and torch.is_grad_enabled() and input_ids.is_cuda and image_feat.is_cuda
-                and self._bf16_heads_ok()):
+        if compact_step and _native.bf16_stream() and image_feat.is_cuda and self._bf16_heads_ok():
             self.bert.__dict__["_bf16_seq_out"] = True
         try:
             sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
@@ -1141,7 +1149,8 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
         if native_losses:
             losses = self._losses_at_labelled_positions(sequence_output_t, sequence_output_v, pooled_output_t,
                                                         pooled_output_v, masked_lm_labels, image_label,
-                                                        image_target, next_sentence_label, gathered)
+                                                        image_target, next_sentence_label, rows=rows, head_t=head_t,
+                                                        head_v=head_v)
             if losses is not None:
                 return losses
         prediction_scores_t, prediction_scores_v, seq_relationship_score = self.cls(
@@ -1183,77 +1192,40 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
 
     def _losses_on_the_bf16_stream(self, sequence_output_t, sequence_output_v, masked_lm_labels, image_label, image_target,
                                    next_sentence_label):
-        """_losses_at_labelled_positions for the bf16 mode: sequence outputs bf16 [B, T, H] / [B, R, Hv] straight from the encoder.
-        Per stream ONE gather of the rows anything behind the encoder reads - _row_map: row 0 of every sample (the poolers),
-        then the labelled rows, every row once - into compact bf16 [rows, H]; the poolers (ReLU, fp32 result) run on its first
-        B rows, the prediction heads (dense + GELU, LayerNorm, decoder) on _row_map's head indices, all on the bf16 kernels;
-        the decoders' logits are fp32 and the losses hand their gradient back in bf16 (autograd_ops.RaggedLinearFn). Backward
-        scatters the compact gradient once per stream into the bf16 gradient of the encoder output. The pooled outputs and
-        everything behind them (alignment head and loss) stay fp32. Returns None when nothing is labelled (exact gather)."""
+        """The three pre-training losses of the bf16 mode (Route C), from the bf16 sequence outputs [B, T, H] / [B, R, Hv] the
+        encoder hands over uncast. Per stream ONE gather of the rows anything behind the encoder reads (_head_row_maps: row 0
+        of every sample, then the _label_rows, every row once) into compact bf16 [rows, H]; the poolers (ReLU, fp32 result)
+        run on its first B rows, the prediction heads (dense + GELU, LayerNorm, decoder) on the head indices, all on the bf16
+        kernels; the decoders' logits are fp32 and the losses hand their gradient back in bf16 (autograd_ops.RaggedLinearFn).
+        Backward scatters the compact gradient once per stream into the bf16 gradient of the encoder output. The pooled
+        outputs and everything behind them (_alignment_loss) stay fp32; the region loss is _region_loss. Returns None when
+        nothing is labelled (exact gather)."""
         cls = self.cls
+        rows = self._label_rows(masked_lm_labels, image_label)
+        if rows is None:
+            return None
         batch, n_tok, n_reg_all = sequence_output_t.size(0), sequence_output_t.size(1), sequence_output_v.size(1)
-        lm_flat = masked_lm_labels.reshape(-1)
-        labelled = image_label == 1
-        per = labelled.reshape(labelled.size(0), -1).size(1)        # regions without the global row 0
-        static = self._static_gather()
-        if not static and self.label_capacity == "auto" and self._auto_capacity is None:
-            frac = max(float((lm_flat != -1).sum()) / max(lm_flat.numel(), 1), float(labelled.sum()) / max(labelled.numel(), 1))
-            self._auto_capacity = min(1.0, 1.2 * frac + 0.01)
-        if static:
-            idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r = self._static_label_rows(masked_lm_labels, image_label)
-        else:
-            idx_t = torch.nonzero(lm_flat != -1).squeeze(1)
-            idx_r = torch.nonzero(labelled.reshape(-1)).squeeze(1)      # index into [B, n_reg_all - 1]
-            if idx_t.numel() == 0 or idx_r.numel() == 0:
-                return None
-            labels_t = lm_flat.index_select(0, idx_t)
-            valid_r, divisor_r = None, float(idx_r.numel())
-            n_t, n_r = idx_t.numel(), idx_r.numel()
-        idx_v = idx_r + torch.div(idx_r, per, rounding_mode="floor") + 1   # same rows inside [B, n_reg_all]
-        map_t, head_t = _row_map(idx_t, n_t, batch, n_tok)
-        map_v, head_v = _row_map(idx_v, n_r, batch, n_reg_all)
+        (map_t, head_t), (map_v, head_v) = _head_row_maps(rows, batch, n_tok, n_reg_all)
         compact_t = F.gather_rows16(sequence_output_t.reshape(batch * n_tok, -1), map_t)
         compact_v = F.gather_rows16(sequence_output_v.reshape(batch * n_reg_all, -1), map_v)
 
         t_pool, v_pool = self.bert.t_pooler.dense, self.bert.v_pooler.dense
         pooled_output_t = F.linear(compact_t[:batch], t_pool.weight, t_pool.bias, act="relu", out_f32=True)
         pooled_output_v = F.linear(compact_v[:batch], v_pool.weight, v_pool.bias, act="relu", out_f32=True)
-        pooled_output = _dropout(_fuse_pooled(cls.fusion_method, pooled_output_t, pooled_output_v), cls.dropout)
-        seq_relationship_score = F.linear(pooled_output, cls.bi_seq_relationship.weight, cls.bi_seq_relationship.bias)
-        next_sentence_loss = F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1),
-                                             ignore_index=-1)
+        next_sentence_loss = self._alignment_loss(pooled_output_t, pooled_output_v, next_sentence_label)
 
         pred = cls.predictions
         logits_t = F.linear(pred.transform(compact_t.index_select(0, head_t)), pred.decoder.weight, pred.bias, out_f32=True)
-        masked_lm_loss = F.cross_entropy(logits_t, labels_t, ignore_index=-1)
+        masked_lm_loss = F.cross_entropy(logits_t, rows.labels_t, ignore_index=-1)
 
         img = cls.imagePredictions
         scores_v = F.linear(img.transform(compact_v.index_select(0, head_v)), img.decoder.weight, img.decoder.bias,
                             out_f32=True)
-        if self.visual_target == 2:
-            count = divisor_r if torch.is_tensor(divisor_r) else torch.full((1,), divisor_r, dtype=torch.float32,
-                                                                          device=scores_v.device)
-            self._nce_seed = A.next_seed()
-            masked_img_loss = F.nce_region_loss(ops._contig(scores_v), image_target, idx_r, valid_r, count, image_target.size(0),
-                                                per, int(self.num_negative * 0.7), int(self.num_negative * 0.3),
-                                                seed=self._nce_seed)
-            return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
-        target = image_target.reshape(-1, image_target.size(-1)).index_select(0, idx_r)
-        if valid_r is not None:
-            target = target * valid_r.unsqueeze(1).to(target.dtype)     # padding rows: all-zero target
-        if self.visual_target == 1:
-            if valid_r is not None:
-                sq = self.vis_criterion(scores_v, target) * valid_r.unsqueeze(1).to(scores_v.dtype)
-                masked_img_loss = torch.sum(sq) / torch.clamp(divisor_r * float(image_target.size(-1)), min=1.0).squeeze(0)
-            else:
-                masked_img_loss = torch.sum(self.vis_criterion(scores_v, target)) / max(
-                    torch.sum(labelled.unsqueeze(2).expand(-1, -1, image_target.size(-1))), 1)
-        else:
-            masked_img_loss = F.kl_div_log_softmax(scores_v, target, divisor_r)
+        masked_img_loss = self._region_loss(scores_v, image_target, rows, image_label)
         return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
 
     def _static_gather(self):
-        """This step gathers the labelled rows into fixed-capacity buffers (no host sync): see _losses_at_labelled_positions."""
+        """This step gathers the labelled rows into fixed-capacity buffers (no host sync): see _label_rows."""
         capturing = torch.cuda.is_current_stream_capturing()
         if not (self.label_capacity is not None or capturing):
             return False
@@ -1271,7 +1243,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
                 and image_target.size(0) >= 2 and image_target.size(1) >= 2)
 
     def _static_label_rows(self, masked_lm_labels, image_label):
-        """Index construction of the fixed-capacity gather -> (idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r): the
+        """Index construction of the fixed-capacity gather (HIP-graph capture, small per-GPU batches) -> _LabelRows: the
         labelled rows are gathered into FIXED-capacity buffers (torch.nonzero_static), the host never learns the counts.
         Padding rows carry label -1 / an all-zero target: they contribute nothing to the losses or to any gradient, and the
         divisors are device scalars. Counts above the capacity would silently drop rows, so they are recorded for
@@ -1300,93 +1272,96 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
             self._label_overflow = torch.zeros(1, dtype=torch.int32, device=n_t.device)
         self._label_overflow.logical_or_(((n_t > cap_t) | (n_r > cap_r)).reshape(1))
         divisor_r = torch.clamp(n_r, max=cap_r).to(torch.float32).reshape(1)
-        return idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r
+        return _LabelRows(idx_t, labels_t, idx_r, valid_r, divisor_r, n_t, n_r)
 
-    def _losses_at_labelled_positions(self, sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v,
-                                      masked_lm_labels, image_label, image_target, next_sentence_label, gathered=None):
-        """The three pre-training losses with the heads evaluated ONLY where a label exists (~15 % of the
-        tokens / regions): CrossEntropy(ignore_index=-1) ignores every other token row and the region loss
-        multiplies every other region row by zero (reference vilbert.py:1506-1522,1578-1585), so the value
-        and every gradient are the same while the [B,T,30522] logits tensor (1.1 GB at B=256) and 85 % of
-        the two decoder GEMMs never exist. Costs one host sync for the row counts (the reference's training
-        loop syncs every step anyway, train_concap.py:589-598). Returns None when nothing is labelled (the
-        caller then takes the reference-shaped path, which yields the reference's NaN).
-        gathered: forward() already built the fixed-capacity indices (_static_label_rows) and ran the last encoder layers on
-        _row_map() rows: the sequence outputs are [rows, H], the heads read them at _row_map()'s head indices."""
-        cls = self.cls
+    def _label_rows(self, masked_lm_labels, image_label):
+        """The rows the prediction heads and the losses read -> _LabelRows, by the fixed-capacity gather where _static_gather()
+        says so and by the exact one (torch.nonzero: one host sync for the row counts; the reference's training loop syncs
+        every step anyway, train_concap.py:589-598) otherwise. The exact gather returns None when no token or no region is
+        labelled: the caller then takes the reference-shaped path, which yields the reference's NaN."""
+        if self._static_gather():
+            return self._static_label_rows(masked_lm_labels, image_label)
         lm_flat = masked_lm_labels.reshape(-1)
-        labelled = image_label == 1
-        per = labelled.reshape(labelled.size(0), -1).size(1)        # regions without the global row 0
-        static = gathered is not None or self._static_gather()
-        if not static and self.label_capacity == "auto" and self._auto_capacity is None:
-            # "auto": the FIRST step counts its labelled rows on the host (one sync, the exact path below) and fixes the gather
+        mask_r = (image_label == 1).reshape(-1)         # index into [B, regions without the global row 0]
+        mask_t = lm_flat != -1
+        if self.label_capacity == "auto" and self._auto_capacity is None:
+            # "auto": the FIRST step counts its labelled rows on the host (one sync, the exact gather below) and fixes the gather
             # capacity at 1.2 x the larger of the two labelled fractions (+ 1 % of the positions); every later step is
             # sync-free. check_label_capacity() - every k steps, off the hot path - raises if a batch ever exceeds it.
-            frac = max(float((lm_flat != -1).sum()) / max(lm_flat.numel(), 1), float(labelled.sum()) / max(labelled.numel(), 1))
+            frac = max(float(mask_t.sum()) / max(mask_t.numel(), 1), float(mask_r.sum()) / max(mask_r.numel(), 1))
             self._auto_capacity = min(1.0, 1.2 * frac + 0.01)
-        if static:
-            # sync-free variant (HIP-graph capture, small per-GPU batches): _static_label_rows
-            if gathered is None:
-                gathered = self._static_label_rows(masked_lm_labels, image_label)
-                compact = False
-            else:
-                compact = True
-            idx_t, labels_t, idx_r, valid_r, divisor_r = gathered[:5]
-        else:
-            idx_t = torch.nonzero(lm_flat != -1).squeeze(1)
-            idx_r = torch.nonzero(labelled.reshape(-1)).squeeze(1)      # index into [B, n_reg_all - 1]
-            if idx_t.numel() == 0 or idx_r.numel() == 0:
+        idx_t, idx_r = (torch.nonzero(mask).squeeze(1) for mask in (mask_t, mask_r))
+        if idx_t.numel() == 0 or idx_r.numel() == 0:
+            return None
+        return _LabelRows(idx_t, lm_flat.index_select(0, idx_t), idx_r, None, float(idx_r.numel()), idx_t.numel(), idx_r.numel())
+
+    def _losses_at_labelled_positions(self, sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v,
+                                      masked_lm_labels, image_label, image_target, next_sentence_label, rows=None,
+                                      head_t=None, head_v=None):
+        """The three pre-training losses on the fp32 stream, with the heads evaluated ONLY where a label exists (~15 % of the
+        tokens / regions): CrossEntropy(ignore_index=-1) ignores every other token row and the region loss multiplies
+        every other region row by zero (reference vilbert.py:1506-1522,1578-1585), so the value and every gradient are the
+        same while the [B,T,30522] logits tensor (1.1 GB at B=256) and 85 % of the two decoder GEMMs never exist.
+        Route A: full sequence outputs [B, S, H]; the heads read them at the _label_rows, and None comes back when nothing
+        is labelled. Route B (rows, head_t, head_v given): forward() built the _label_rows before the encoder and ran its
+        last layers on _head_row_maps: the sequence outputs are [rows, H], the heads read them at those head indices.
+        The alignment and the region loss are _alignment_loss and _region_loss."""
+        cls = self.cls
+        if rows is None:
+            rows = self._label_rows(masked_lm_labels, image_label)
+            if rows is None:
                 return None
-            labels_t = lm_flat.index_select(0, idx_t)
-            valid_r = None
-            divisor_r = float(idx_r.numel())
-            compact = False
-        idx_v = idx_r + torch.div(idx_r, per, rounding_mode="floor") + 1   # same rows inside [B, n_reg_all]
+            per = image_label.reshape(image_label.size(0), -1).size(1)       # regions without the global row 0
+            head_t, head_v = rows.idx_t, _with_global_row(rows.idx_r, per)
+            sequence_output_t = sequence_output_t.reshape(-1, sequence_output_t.size(-1))
+            sequence_output_v = sequence_output_v.reshape(-1, sequence_output_v.size(-1))
+        next_sentence_loss = self._alignment_loss(pooled_output_t, pooled_output_v, next_sentence_label)
+        logits_t = cls.predictions(sequence_output_t.index_select(0, head_t), pad_cols=True)
+        masked_lm_loss = F.cross_entropy(logits_t, rows.labels_t, ignore_index=-1)
+        scores_v = cls.imagePredictions(sequence_output_v.index_select(0, head_v))
+        masked_img_loss = self._region_loss(scores_v, image_target, rows, image_label)
+        return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
 
+    def _alignment_loss(self, pooled_output_t, pooled_output_v, next_sentence_label):
+        """Image-text alignment loss from the two fp32 pooled outputs: fuse, dropout, 2-wide linear, cross-entropy."""
+        cls = self.cls
         pooled_output = _dropout(_fuse_pooled(cls.fusion_method, pooled_output_t, pooled_output_v), cls.dropout)
-        seq_relationship_score = F.linear(pooled_output, cls.bi_seq_relationship.weight,
-                                          cls.bi_seq_relationship.bias)
+        seq_relationship_score = F.linear(pooled_output, cls.bi_seq_relationship.weight, cls.bi_seq_relationship.bias)
         # losses: native row kernels (csrc/loss.hip) - log-sum-exp forward, (softmax - onehot) backward
-        next_sentence_loss = F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1),
-                                             ignore_index=-1)
+        return F.cross_entropy(seq_relationship_score.view(-1, 2), next_sentence_label.reshape(-1), ignore_index=-1)
 
-        if compact:
-            rows_t = sequence_output_t.index_select(0, gathered[7])
-        else:
-            rows_t = sequence_output_t.reshape(-1, sequence_output_t.size(-1)).index_select(0, idx_t)
-        masked_lm_loss = F.cross_entropy(cls.predictions(rows_t, pad_cols=True), labels_t, ignore_index=-1)
-
-        if compact:
-            rows_v = sequence_output_v.index_select(0, gathered[8])
-        else:
-            rows_v = sequence_output_v.reshape(-1, sequence_output_v.size(-1)).index_select(0, idx_v)
-        scores_v = cls.imagePredictions(rows_v)
+    def _region_loss(self, scores_v, image_target, rows, image_label):
+        """Masked-region loss of visual target 0 (KL), 1 (squared error) or 2 (NCE) from the image head's fp32 scores_v at the
+        _LabelRows `rows`; padding rows of the fixed-capacity gather add nothing to the value or to any gradient."""
+        dim = image_target.size(-1)
         if self.visual_target == 2:
             # NCE against sampled negative region features (csrc/nce.hip): the candidate rows are read in place in the flat
             # target table, the negatives are a function of (seed, region) - the same for either gather
-            count = divisor_r if torch.is_tensor(divisor_r) else torch.full((1,), divisor_r, dtype=torch.float32,
-                                                                          device=scores_v.device)
+            count = rows.divisor_r if torch.is_tensor(rows.divisor_r) else torch.full(
+                (1,), rows.divisor_r, dtype=torch.float32, device=scores_v.device)
+            per = image_label.reshape(image_label.size(0), -1).size(1)       # regions without the global row 0
             self._nce_seed = A.next_seed()
-            masked_img_loss = F.nce_region_loss(scores_v, image_target, idx_r, valid_r, count, image_target.size(0), per,
-                                                int(self.num_negative * 0.7), int(self.num_negative * 0.3),
-                                                seed=self._nce_seed)
-            return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
-        target = image_target.reshape(-1, image_target.size(-1)).index_select(0, idx_r)
-        if valid_r is not None:
-            target = target * valid_r.unsqueeze(1).to(target.dtype)     # padding rows: all-zero target
-        if self.visual_target == 1:
-            if valid_r is not None:
-                # a zero target does not silence a padding row of the squared error: the row's terms are multiplied by
-                # zero (so it gets no gradient either); the divisor stays on the device: max(rows used * dim, 1)
-                sq = self.vis_criterion(scores_v, target) * valid_r.unsqueeze(1).to(scores_v.dtype)
-                masked_img_loss = torch.sum(sq) / torch.clamp(divisor_r * float(image_target.size(-1)), min=1.0).squeeze(0)
-            else:
-                masked_img_loss = torch.sum(self.vis_criterion(scores_v, target)) / max(
-                    torch.sum(labelled.unsqueeze(2).expand(-1, -1, image_target.size(-1))), 1)
-        else:
+            # (_contig: the ragged decoder of the bf16 route may hand over a strided view; a contiguous tensor passes as it is)
+            return F.nce_region_loss(ops._contig(scores_v), image_target, rows.idx_r, rows.valid_r, count,
+                                     image_target.size(0), per, int(self.num_negative * 0.7), int(self.num_negative * 0.3),
+                                     seed=self._nce_seed)
+        target = image_target.reshape(-1, dim).index_select(0, rows.idx_r)
+        if rows.valid_r is not None:
+            target = target * rows.valid_r.unsqueeze(1).to(target.dtype)     # padding rows: all-zero target
+        if self.visual_target == 0:
             # divisor: the reference's max(sum(image_label == 1), 0) (:1520-1522) = the number of rows here
-            masked_img_loss = F.kl_div_log_softmax(scores_v, target, divisor_r)
-        return masked_lm_loss.unsqueeze(0), masked_img_loss.unsqueeze(0), next_sentence_loss.unsqueeze(0)
+            return F.kl_div_log_softmax(scores_v, target, rows.divisor_r)
+        sq = self.vis_criterion(scores_v, target)
+        if rows.valid_r is not None:
+            # a zero target does not silence a padding row of the squared error: the row's terms are multiplied by
+            # zero (so it gets no gradient either); the divisor stays on the device: max(rows used * dim, 1)
+            sq = sq * rows.valid_r.unsqueeze(1).to(scores_v.dtype)
+            divisor = torch.clamp(rows.divisor_r * float(dim), min=1.0).squeeze(0)
+        else:
+            # exact gather: at least one row, so the reference's max(count * dim, 1) (:1506-1512) is count * dim. A device
+            # scalar like the one above: torch divides by a host scalar as a product with its reciprocal, which rounds otherwise
+            divisor = scores_v.new_full((), rows.divisor_r * dim)
+        return torch.sum(sq) / divisor
 
     def check_label_capacity(self):
         """Raises if the last fixed-capacity label gather overflowed (synchronises; call it off the hot path)."""
