@@ -90,6 +90,8 @@ def _rebind_task_utils(module):
     module.LossMap["BCEWithLogitLoss"] = task_losses.BCEWithLogitsLoss(reduction="mean")
     module.LossMap["CrossEntropyLoss"] = task_losses.CrossEntropyLoss()
     module.compute_score_with_logits = task_losses.compute_score_with_logits
+    # one added name: which output of VILBertForVLTasks each task type reads (for model.set_active_heads)
+    module.HEAD_OF_TASK_TYPE = task_losses.HEAD_OF_TASK_TYPE
 
 
 class _OptimizationFinder(object):

@@ -401,6 +401,16 @@ HEADS_SIGNATURES = {
     "vbh_mul_bf16": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P, _I64]),
 }
 
+# include/vilbert_hip_finetune.h (the skinny-output linear of the fine-tuning heads on the bf16 stream; prefix vbf_), mirrored
+# one to one (checked by tests/test_finetune16_abi.py)
+FINETUNE_SIGNATURES = {
+    "vbf_skinny_linear_fwd": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _P, _P, _I64, _F32, _U64]),
+    "vbf_skinny_linear_bwd_input": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _F32, _U64]),
+    "vbf_skinny_wgrad_workspace": (_I64, [_I64, _I32, _I32]),
+    "vbf_skinny_linear_bwd_weight": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _P, _F32, _U64]),
+    "vbf_cast_rows_colsum": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P]),
+}
+
 _lib = None
 
 
@@ -415,7 +425,7 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
-                                  + list(HEADS_SIGNATURES.items())):
+                                  + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

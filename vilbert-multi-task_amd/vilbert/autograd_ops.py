@@ -265,12 +265,16 @@ class RaggedLinearFn(Function):
     1,601-wide region decoder): the bf16 kernels on the zero-padded shadow (ops16.linear_ragged_*). y is an fp32 [rows, n] view
     of a [rows, n_pad] buffer. The output carries `_vb_ragged`: a loss node that reads it directly (CrossEntropyFn, KLDivFn)
     then hands over its gradient as the padded bf16 operands G (and G^T) these GEMMs take - a NaN placeholder travels through
-    autograd in their place (`_vb_grad16`). Any other gradient arrives in fp32 and is rounded here."""
+    autograd in their place (`_vb_grad16`). Any other gradient arrives in fp32 and is rounded here. bias_grad_f32 (the decoders
+    of VILBertForVLTasks, whose gradient always arrives that way): the bias gradient is then the fp32 column sum of that
+    gradient BEFORE the rounding, left behind by the cast (ops16.cast_rows_colsum) - as the fp32-tensor path sums it; without
+    it the weight-gradient kernel sums the rounded operand."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, bias_grad_f32=False):
         y = ops16.linear_ragged_fwd(x, weight, bias)
         ctx.save_for_backward(x, weight, *([bias] if bias is not None else []))
+        ctx.bias_grad_f32 = bool(bias_grad_f32)
         y._vb_ragged = True
         return y
 
@@ -289,9 +293,14 @@ class RaggedLinearFn(Function):
             dy2 = dy.reshape(rows, n)
             if dy2.stride(1) != 1 or dy2.stride(0) % 4 != 0 or dy2.data_ptr() % 16 != 0:
                 dy2 = dy2.contiguous() if n % 4 == 0 else torch.nn.functional.pad(dy2, (0, 4 - n % 4))[:, :n]
-            G, GT = torch.empty(rows, n_pad, dtype=BF16, device=dy.device), None
-            N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), rows, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
-                                                  G.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
+            GT = None
+            if ctx.bias_grad_f32 and bias is not None and ctx.needs_input_grad[2]:
+                # with the fp32 column sums of the gradient from the same pass: the bias gradient is not summed from rounded values
+                G, part = ops16.cast_rows_colsum(dy2)
+            else:
+                G = torch.empty(rows, n_pad, dtype=BF16, device=dy.device)
+                N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), rows, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
+                                                      G.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = ops16.linear_ragged_bwd_input(G, GT, weight, bias, rows).view(x.shape)
@@ -308,7 +317,41 @@ class RaggedLinearFn(Function):
                 ops16.linear_ragged_bwd_weight(dy_, x_, seg_n_, want_b, dw_out, db_out)
             (dw,), (db_w,) = _wgrad(G, x, [weight], [bias], [need_w], [need_b], launcher)
             db = db_w if need_b else db
-        return dx, dw, db
+        return dx, dw, db, None
+
+
+class SkinnyLinearFn(Function):
+    """y fp32 [..., n] = dropout(x, p) @ W.T + b + row_add for a bf16 x and n <= 4 outputs (`vision_logit`, `linguisic_logit` of
+    VILBertForVLTasks; ops16.skinny_*): the dropped input is never materialised - forward, input gradient and weight gradient
+    regenerate the mask from the saved (p, seed) over x itself. W is the fp32 master weight (no shadow). row_add (one fp32
+    value per row, the additive region mask) gets no gradient. The weight gradient goes where LinearFn's goes (_wgrad: arena
+    slices, side stream)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, row_add, drop_p):
+        seed = next_seed() if drop_p > 0.0 else 0
+        y = ops16.skinny_fwd(x, weight, bias, row_add, drop_p, seed)
+        ctx.save_for_backward(x, weight, *([bias] if bias is not None else []))
+        ctx.drop = (drop_p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors[:2]
+        bias = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+        p, seed = ctx.drop
+        dy = dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = ops16.skinny_bwd_input(dy, weight, p, seed).view(x.shape)
+        need_w = bool(ctx.needs_input_grad[1])
+        need_b = bool(bias is not None and ctx.needs_input_grad[2])
+        if need_w or need_b:
+            launcher = lambda dy_, x_, nseg_, seg_n_, want_b, dw_out=None, db_out=None: \
+                ops16.skinny_bwd_weight(dy_, x_, seg_n_, want_b[0], dw_out[0] if dw_out else None,
+                                        db_out[0] if db_out else None, p, seed)
+            (dw,), (db,) = _wgrad(dy, x, [weight], [bias], [need_w], [need_b], launcher)
+        return dx, dw, db, None, None
 
 
 def _grad16_placeholder(like, payload):

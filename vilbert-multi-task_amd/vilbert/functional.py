@@ -49,11 +49,14 @@ def _uniform_bias(biases):
     return all(b is None for b in biases) or all(b is not None for b in biases)
 
 
-def linear(x, weights, biases=None, act=None, residual=None, drop_p=0.0, pad_cols=False, out="f32", out_f32=False):
+def linear(x, weights, biases=None, act=None, residual=None, drop_p=0.0, pad_cols=False, out="f32", out_f32=False,
+           bias_grad_f32=False):
     """dropout(act(x @ cat(weights).T + cat(biases)), drop_p) (+ residual); weights / biases may be single
     tensors; drop_p is the EFFECTIVE probability (0 in eval mode). pad_cols, out: see ops.linear_fwd (out is a request
     the MX inference mode honours where the shape allows it; everywhere else the result is an fp32 tensor). On the bf16
-    stream the result is bf16, or fp32 with out_f32."""
+    stream the result is bf16, or fp32 with out_f32. bias_grad_f32: autograd_ops.RaggedLinearFn (a decoder of ragged width
+    on the bf16 stream). It is IGNORED everywhere else - in particular for a decoder whose width is a tile multiple, which takes
+    the LinearFn route and sums its bias gradient from the bf16-rounded gradient."""
     if not isinstance(weights, (list, tuple)):
         weights, biases = [weights], [biases]
     if biases is None:
@@ -69,7 +72,7 @@ def linear(x, weights, biases=None, act=None, residual=None, drop_p=0.0, pad_col
             # an output width that is no tile multiple (the 30,522-wide MLM decoder, the 1,601-wide region decoder): the bf16
             # kernels on a zero-padded shadow, fp32 result
             if grad:
-                return A.RaggedLinearFn.apply(x, weights[0], biases[0])
+                return A.RaggedLinearFn.apply(x, weights[0], biases[0], bias_grad_f32)
             return ops16.linear_ragged_fwd(x, weights[0], biases[0])
         # under autograd an activation stays on the bf16 kernels where its backward has one: GELU with a bf16 result (the
         # saved derivative is multiplied in), ReLU with an fp32 result (masked by the output); swish, and VB_BF16_HEADS=0,
@@ -86,6 +89,14 @@ def linear(x, weights, biases=None, act=None, residual=None, drop_p=0.0, pad_col
     if kern is ops16:
         return ops16.linear_fwd(x, weights, biases, act, residual, drop_p=drop_p, seed=seed, out_f32=out_f32)[0]
     return ops.linear_fwd(x, weights, biases, act, residual, drop_p=drop_p, seed=seed, pad_cols=pad_cols, out=out)[0]
+
+
+def skinny_linear(x, weight, bias=None, row_add=None, drop_p=0.0):
+    """dropout(x, drop_p) @ weight.T + bias + row_add[..., None] -> fp32 [..., n] for a bf16 x and a weight of 1 .. 4 rows
+    (ops16.skinny_ok): the dropout is drawn inside the kernels, drop_p is the EFFECTIVE probability."""
+    if _needs_grad(x, weight, bias):
+        return A.SkinnyLinearFn.apply(x, weight, bias, row_add, drop_p)
+    return ops16.skinny_fwd(x, weight, bias, row_add, drop_p, A.next_seed() if drop_p > 0.0 else 0)
 
 
 def linear_f32_out(x, weight, bias):

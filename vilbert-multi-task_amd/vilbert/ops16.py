@@ -403,6 +403,20 @@ def colsum_parts(part, n, out=None):
     return out
 
 
+def cast_rows_colsum(dy):
+    """The fp32 gradient dy [rows, n] of a ragged decoder's logits (row stride % 4 == 0, 16-byte aligned) -> (G bf16 [rows, n_pad],
+    pad columns zero; fp32 [ceil(rows / 64), n_pad] column sums of the UNROUNDED gradient per 64 rows - colsum_parts adds them up:
+    the decoder's bias gradient in fp32). One pass over dy (csrc/finetune16.hip)."""
+    rows, n = dy.shape
+    n_pad = padded(n)
+    ld = dy.stride(0) if rows > 1 else max(n, dy.stride(0))
+    G = torch.empty(rows, n_pad, dtype=BF16, device=dy.device)
+    part = torch.empty((rows + 63) // 64, n_pad, dtype=torch.float32, device=dy.device)
+    N.check(N.lib().vbf_cast_rows_colsum(N.stream_ptr(), rows, n, N.dev_f32(dy, "linear grad_output"), ld, G.data_ptr(), n_pad,
+                                         part.data_ptr()), "vbf_cast_rows_colsum")
+    return G, part
+
+
 def kl_bwd16(grad_loss, scores, target, lse, tsum, divisor):
     """The KL gradient as bf16 G [rows, n_pad] (pad columns zero); scores fp32 [rows, n] (row-strided view allowed)."""
     if not ops._row_strided(scores):
@@ -540,6 +554,113 @@ def linear_ragged_bwd_weight(G, x, n, want_bias, dw_out=None, db_out=None):
     a.dbias[0] = N.dev_f32(dbs[0], "bias gradient") if dbs[0] is not None else None
     ops._timed(lambda: N.check(N.lib().vb_wgrad_bf16(N.stream_ptr(), ctypes.byref(a)), "vb_wgrad_bf16 (ragged)"),
                2.0 * M * n * K, ("wgrad16", M, n, K, 1))
+    return dws, dbs
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The skinny-output linear of the fine-tuning heads (csrc/finetune16.hip, include/vilbert_hip_finetune.h): 1 .. 4 outputs per
+# bf16 row (`vision_logit`, `linguisic_logit` of VILBertForVLTasks), the input dropout drawn inside the kernels, the fp32
+# master weight read as it is (no shadow).
+# ---------------------------------------------------------------------------------------------------------------
+SKINNY_MAX_N, SKINNY_MAX_K = 4, 2048      # VBF_MAX_N, VBF_MAX_K
+
+
+def skinny_ok(K, n):
+    """Shapes the skinny-output kernels serve."""
+    return 1 <= n <= SKINNY_MAX_N and 8 <= K <= SKINNY_MAX_K and K % 8 == 0
+
+
+def _skinny_weight(weight):
+    w = weight.detach()
+    if w.dim() != 2 or not w.is_contiguous() or not skinny_ok(w.shape[1], w.shape[0]):
+        raise RuntimeError("skinny linear: a contiguous weight [n <= %d, K <= %d, K %% 8 == 0] expected, got %s"
+                           % (SKINNY_MAX_N, SKINNY_MAX_K, tuple(weight.shape)))
+    return w, w.shape[0], w.shape[1]
+
+
+def _rows32(t, n, what):
+    """(2-D row-strided fp32 view [rows, n], row stride) of a [..., n] tensor; copies only if it has to."""
+    if not (ops._row_strided(t) and t.data_ptr() % 16 == 0):
+        t = ops._contig(t).view(-1, n)
+    N.dev_f32(t, what)
+    return t, (t.stride(0) if t.shape[0] > 1 else max(n, t.stride(0)))
+
+
+def skinny_fwd(x, weight, bias=None, row_add=None, drop_p=0.0, seed=0, out=None):
+    """dropout(x, drop_p) @ weight.T + bias + row_add[:, None] -> fp32 [..., n]. x bf16 [..., K] (a 2-D row-strided view is read
+    in place), weight fp32 [n, K], bias fp32 [n] or None, row_add fp32 with one value per row or None. The mask is that of
+    vb_dropout over the dense [rows, K] tensor. out: a 2-D fp32 [rows, n] target (row stride >= n) or None."""
+    w, n, K = _skinny_weight(weight)
+    if x.shape[-1] != K:
+        raise RuntimeError("skinny linear: input has %d features, weight expects %d" % (x.shape[-1], K))
+    lead = tuple(x.shape[:-1])
+    x2, ldx = _rows16(x, "skinny linear input")
+    rows = x2.shape[0]
+    if out is None:
+        out = torch.empty(lead + (n,), dtype=torch.float32, device=x.device)
+        o2, ldo = out.view(-1, n), n
+    else:
+        if out.shape != (rows, n) or not ops._row_strided(out):
+            raise RuntimeError("skinny linear: out must be a row-strided [rows, n] tensor")
+        o2, ldo = out, (out.stride(0) if rows > 1 else max(n, out.stride(0)))
+    if row_add is not None:
+        row_add = ops._contig(row_add)
+        if row_add.numel() != rows:
+            raise RuntimeError("skinny linear: row_add needs one value per row")
+    N.check(N.lib().vbf_skinny_linear_fwd(
+        N.stream_ptr(), rows, K, n, x2.data_ptr(), ldx, N.dev_f32(w, "skinny linear weight"), K,
+        N.dev_f32(ops._contig(bias.detach()), "skinny linear bias") if bias is not None else None,
+        N.dev_f32(row_add, "skinny linear row_add"), N.dev_f32(o2, "skinny linear output"), ldo, float(drop_p), int(seed)),
+        "vbf_skinny_linear_fwd")
+    return out
+
+
+def skinny_bwd_input(dy, weight, drop_p=0.0, seed=0, out=None):
+    """dX bf16 [..., K] = dropout-mask * scale * (dY @ weight); dy fp32 [..., n]. out: a 2-D bf16 [rows, K] target (row stride
+    >= K, a multiple of 8) or None."""
+    w, n, K = _skinny_weight(weight)
+    lead = tuple(dy.shape[:-1])
+    dy2, ldy = _rows32(dy, n, "skinny linear grad_output")
+    rows = dy2.shape[0]
+    if out is None:
+        out = torch.empty(lead + (K,), dtype=BF16, device=dy.device)
+        d2, ldd = out.view(-1, K), K
+    else:
+        if out.shape != (rows, K) or not ops._row_strided(out):
+            raise RuntimeError("skinny linear: out must be a row-strided [rows, K] tensor")
+        d2, ldd = out, (out.stride(0) if rows > 1 else max(K, out.stride(0)))
+    N.check(N.lib().vbf_skinny_linear_bwd_input(
+        N.stream_ptr(), rows, K, n, dy2.data_ptr(), ldy, N.dev_f32(w, "skinny linear weight"), K, dev_bf16(d2, "skinny linear dx"),
+        ldd, float(drop_p), int(seed)), "vbf_skinny_linear_bwd_input")
+    return out
+
+
+_SKINNY_WS = {}
+
+
+def skinny_bwd_weight(dy, x, n, want_bias, dw_out=None, db_out=None, drop_p=0.0, seed=0):
+    """dW [n, K] += dY^T dropout(x), db [n] += colsum(dY): ADDED into the targets, as linear_bwd_weight does (nseg = 1; targets
+    not given are zero-filled here). dy fp32 [..., n], x bf16 [..., K]. Two launches through a per-(device, stream) workspace
+    (grow-only, like the LayerNorm backward's), bit-identical from run to run. Returns ([dW], [db or None])."""
+    K = x.shape[-1]
+    if not skinny_ok(K, n):
+        raise RuntimeError("skinny linear: shape (K = %d, n = %d) is not served" % (K, n))
+    x2, ldx = _rows16(x, "skinny linear input")
+    dy2, ldy = _rows32(dy, n, "skinny linear grad_output")
+    rows = x2.shape[0]
+    if dy2.shape[0] != rows:
+        raise RuntimeError("skinny linear: row count mismatch")
+    dws, dbs = ops.wgrad_targets(1, n, K, [bool(want_bias)], [dw_out] if dw_out is not None else None,
+                                 [db_out] if db_out is not None else None, x.device)
+    floats = N.lib().vbf_skinny_wgrad_workspace(rows, K, n)
+    key = (x.device.index, N.raw_stream(x.device.index))
+    ws = _SKINNY_WS.get(key)
+    if ws is None or ws.numel() < floats:
+        ws = _SKINNY_WS[key] = torch.empty(max(floats, 1 << 20), dtype=torch.float32, device=x.device)
+    N.check(N.lib().vbf_skinny_linear_bwd_weight(
+        N.stream_ptr(), rows, K, n, dy2.data_ptr(), ldy, x2.data_ptr(), ldx, N.dev_f32(dws[0], "weight gradient"), K,
+        N.dev_f32(dbs[0], "bias gradient") if dbs[0] is not None else None, ws.data_ptr(), float(drop_p), int(seed)),
+        "vbf_skinny_linear_bwd_weight")
     return dws, dbs
 
 

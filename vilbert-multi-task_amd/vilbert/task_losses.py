@@ -14,6 +14,20 @@ from . import ops
 from .autograd_ops import BCEWithLogitsFn, CrossEntropyFn
 
 
+# The output of VILBertForVLTasks.forward that ForwardModelsTrain reads per `task_cfg[task]["type"]` (task_utils.py:325-374):
+# what a trainer passes to `model.set_active_heads([...])` so that a step computes that head alone. Also bound into the
+# reference's module as `vilbert.task_utils.HEAD_OF_TASK_TYPE`.
+HEAD_OF_TASK_TYPE = {
+    "VL-classifier": "vil_prediction",
+    "VL-classifier-GQA": "vil_prediction_gqa",
+    "VL-logit": "vil_logit",
+    "V-logit": "vision_logit",
+    "V-logit-mc": "vision_logit",
+    "VL-binary-classifier": "vil_binary_prediction",
+    "VL-tri-classifier": "vil_tri_prediction",
+}
+
+
 def _fp32_hip(t):
     return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32
 

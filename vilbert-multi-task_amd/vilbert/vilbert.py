@@ -1422,8 +1422,36 @@ class GeLU(nn.Module):
         raise RuntimeError("GeLU is fused into the preceding GEMM; call SimpleClassifier.forward")
 
 
+# The nine outputs of VILBertForVLTasks.forward, in the order of the returned tuple (the tenth element is the attention maps)
+VLTASK_HEADS = ("vil_prediction", "vil_prediction_gqa", "vil_logit", "vil_binary_prediction", "vil_tri_prediction",
+                "vision_prediction", "vision_logit", "linguisic_prediction", "linguisic_logit")
+# ... those computed from the fused pooled output (B rows)
+_POOLED_HEADS = frozenset(VLTASK_HEADS[:5])
+_FIRST_ROW_MAPS = {}
+
+
+def _first_row_map(batch, per_sample, device):
+    """int32 [batch]: row 0 of every sample inside the flat [batch * per_sample, H] encoder output (the rows the poolers read).
+    Built on the device, once per shape (no host sync); a map built while a stream is being captured is not kept."""
+    key = (device, batch, per_sample)
+    m = _FIRST_ROW_MAPS.get(key)
+    if m is None:
+        m = torch.arange(batch, device=device, dtype=torch.int32) * per_sample
+        if not torch.cuda.is_current_stream_capturing():
+            _FIRST_ROW_MAPS[key] = m
+    return m
+
+
+def _skip_dropout_seed(dropout_module):
+    """A dropout site whose head is not computed still draws its seed: the masks of the computed heads do not depend on which
+    heads are selected (set_active_heads)."""
+    if _drop_p(dropout_module) > 0.0:
+        A.next_seed()
+
+
 class VILBertForVLTasks(BertPreTrainedModel):
-    """Multi-task wrapper: every head is computed on every forward, reference vilbert.py:1600-1708."""
+    """Multi-task wrapper, reference vilbert.py:1600-1708: by default every head is computed on every forward, as there.
+    `set_active_heads` names the heads a step needs; the others are None in the returned tuple and launch nothing."""
 
     def __init__(self, config, num_labels, dropout_prob=0.1, default_gpu=True):
         super(VILBertForVLTasks, self).__init__(config)
@@ -1439,36 +1467,140 @@ class VILBertForVLTasks(BertPreTrainedModel):
         self.vision_logit = nn.Linear(config.v_hidden_size, 1)
         self.linguisic_logit = nn.Linear(config.hidden_size, 1)
         self.fusion_method = config.fusion_method
+        self.active_heads = None        # None: all nine (set_active_heads)
         self.apply(self.init_weights)
         self.tie_weights()
 
     def tie_weights(self):
         self._tie_or_clone_weights(self.cls.predictions.decoder, self.bert.embeddings.word_embeddings)
 
+    def set_active_heads(self, names=None):
+        """Which of the nine outputs (VLTASK_HEADS) the following forwards compute: a name or an iterable of names; None (the
+        default) = all of them, the reference's behaviour. An unselected head is None in the returned tuple and launches
+        nothing - in every mode and phase. The reference's trainer reads ONE output per task type
+        (vilbert.task_losses.HEAD_OF_TASK_TYPE). Stored as `active_heads` (a tuple in output order, or None); parameters,
+        state_dict and the forward signature are untouched. A dropout site of an unselected head still draws its seed, so
+        the masks of the selected heads are those of the all-heads forward."""
+        if names is None:
+            self.active_heads = None
+            return
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in VLTASK_HEADS]
+        if unknown:
+            raise ValueError("set_active_heads: unknown head name(s) %s - valid names: %s"
+                             % (", ".join(repr(n) for n in unknown), ", ".join(VLTASK_HEADS)))
+        self.active_heads = tuple(n for n in VLTASK_HEADS if n in names)
+
+    def _bf16_heads_ok(self):
+        """Sibling of BertForMultiModalPreTraining._bf16_heads_ok for the heads of this wrapper: poolers, prediction-head
+        transforms (GELU) and decoders pass the shape rules of the bf16 kernels, the two 1-wide logits those of the
+        skinny-output kernels, and VB_BF16_HEADS is not 0."""
+        from . import ops16
+        c = self.config
+        H, Hv, Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
+        pred, img = self.cls.predictions, self.cls.imagePredictions
+
+        def out_ok(K, n):
+            return ops16.eligible(K, n) or ops16.ragged_ok(K, n)
+        return (ops16.heads_enabled() and ops16.eligible(H, Hb, act="relu") and ops16.eligible(Hv, Hb, act="relu")
+                and ops16.eligible(H, H) and ops16.eligible(Hv, Hv) and H <= 1024 and Hv <= 1024
+                and pred.transform.transform_act_fn == "gelu" and img.transform.transform_act_fn == "gelu"
+                and out_ok(H, pred.decoder.weight.size(0)) and out_ok(Hv, c.v_target_size)
+                and ops16.skinny_ok(H, self.linguisic_logit.weight.size(0))
+                and ops16.skinny_ok(Hv, self.vision_logit.weight.size(0)))
+
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, co_attention_mask=None, task_ids=None,
                 output_all_encoded_layers=False, output_all_attention_masks=False):
         from . import ops
-        sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
-            input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
-            co_attention_mask, task_ids, output_all_encoded_layers=output_all_encoded_layers,
-            output_all_attention_masks=output_all_attention_masks)
+        heads = getattr(self, "active_heads", None)
+        want = frozenset(VLTASK_HEADS if heads is None else heads)
+        # bf16 mode, training step: poolers and heads stay on the bf16 stream - the encoder's bf16 outputs come back as they
+        # are, without the fp32 casts of the two full hidden states (and of their gradients). Evaluation, fp32 / fp8 / MX,
+        # widths the bf16 kernels do not serve, CPU tensors, attention maps or all layers asked for: the path below, as before.
+        if (_native.bf16_stream() and self.training and torch.is_grad_enabled() and input_txt.is_cuda and input_imgs.is_cuda
+                and not output_all_encoded_layers and not output_all_attention_masks and not self.config.dynamic_attention
+                and self._bf16_heads_ok()):
+            self.bert.__dict__["_bf16_seq_out"] = True
+        try:
+            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v, all_attention_mask = self.bert(
+                input_txt, input_imgs, image_loc, token_type_ids, attention_mask, image_attention_mask,
+                co_attention_mask, task_ids, output_all_encoded_layers=output_all_encoded_layers,
+                output_all_attention_masks=output_all_attention_masks)
+        finally:
+            self.bert.__dict__.pop("_bf16_seq_out", None)
+        on16 = pooled_output_t is None      # the encoder handed its bf16 outputs over uncast: pooling is done here
+        batch = input_txt.size(0)
+        # the alignment score of self.cls: with all heads (the reference computes it), or where it is what comes back as
+        # vil_binary_prediction - an odd batch (:1686-1689)
+        want_nsp = heads is None or ("vil_binary_prediction" in want and batch % 2 != 0)
+        if on16 and (want_nsp or want & _POOLED_HEADS):
+            # row 0 of every sample, gathered in bf16 (backward: one scatter per stream), ReLU pooler with an fp32 result
+            n_tok, n_reg = sequence_output_t.size(1), sequence_output_v.size(1)
+            t_pool, v_pool = self.bert.t_pooler.dense, self.bert.v_pooler.dense
+            first_t = F.gather_rows16(sequence_output_t.reshape(batch * n_tok, -1), _first_row_map(batch, n_tok, input_txt.device))
+            first_v = F.gather_rows16(sequence_output_v.reshape(batch * n_reg, -1), _first_row_map(batch, n_reg, input_txt.device))
+            pooled_output_t = F.linear(first_t, t_pool.weight, t_pool.bias, act="relu", out_f32=True)
+            pooled_output_v = F.linear(first_v, v_pool.weight, v_pool.bias, act="relu", out_f32=True)
 
-        linguisic_prediction, vision_prediction, vil_binary_prediction = self.cls(
-            sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v)
-        pooled_output = _dropout(_fuse_pooled(self.fusion_method, pooled_output_t, pooled_output_v), self.dropout)
+        cls = self.cls
+        if heads is None and not on16:
+            linguisic_prediction, vision_prediction, vil_binary_prediction = cls(
+                sequence_output_t, sequence_output_v, pooled_output_t, pooled_output_v)
+        else:
+            # the parts of self.cls that are asked for, in its order. On the bf16 stream the prediction heads run on the bf16
+            # kernels: dense + GELU and LayerNorm in bf16, the decoder on its zero-padded shadow with an fp32 result
+            linguisic_prediction = vision_prediction = vil_binary_prediction = None
+            if want_nsp:
+                nsp_in = _dropout(_fuse_pooled(cls.fusion_method, pooled_output_t, pooled_output_v), cls.dropout)
+            else:
+                _skip_dropout_seed(cls.dropout)
+            if "linguisic_prediction" in want:
+                pred = cls.predictions
+                linguisic_prediction = pred(sequence_output_t) if not on16 else F.linear(
+                    pred.transform(sequence_output_t), pred.decoder.weight, pred.bias, out_f32=True, bias_grad_f32=True)
+            if want_nsp:
+                vil_binary_prediction = F.linear(nsp_in, cls.bi_seq_relationship.weight, cls.bi_seq_relationship.bias)
+            if "vision_prediction" in want:
+                img = cls.imagePredictions
+                vision_prediction = img(sequence_output_v) if not on16 else F.linear(
+                    img.transform(sequence_output_v), img.decoder.weight, img.decoder.bias, out_f32=True, bias_grad_f32=True)
 
-        vil_prediction = self.vil_prediction(pooled_output)
-        vil_prediction_gqa = self.vil_prediction_gqa(pooled_output)
-        if pooled_output.size(0) % 2 == 0:  # otherwise the NSP score from self.cls leaks through (:1686-1689)
+        vil_prediction = vil_prediction_gqa = vil_logit = vil_tri_prediction = vision_logit = linguisic_logit = None
+        if want & _POOLED_HEADS:
+            pooled_output = _dropout(_fuse_pooled(self.fusion_method, pooled_output_t, pooled_output_v), self.dropout)
+        else:
+            _skip_dropout_seed(self.dropout)
+        if "vil_prediction" in want:
+            vil_prediction = self.vil_prediction(pooled_output)
+        if "vil_prediction_gqa" in want:
+            vil_prediction_gqa = self.vil_prediction_gqa(pooled_output)
+        if "vil_binary_prediction" not in want:
+            vil_binary_prediction = None
+        elif batch % 2 == 0:  # otherwise the NSP score from self.cls leaks through (:1686-1689)
             vil_binary_prediction = self.vil_binary_prediction(pooled_output.view(-1, pooled_output.size(1) * 2))
-        vil_logit = F.linear(pooled_output, self.vil_logit.weight, self.vil_logit.bias)
-        vil_tri_prediction = F.linear(pooled_output, self.vil_tri_prediction.weight, self.vil_tri_prediction.bias)
-        # like the reference this needs image_attention_mask (:1692-1694 crash on None)
-        region_mask = ops.additive_mask(image_attention_mask).unsqueeze(2)
-        vision_logit = F.linear(_dropout(sequence_output_v, self.dropout), self.vision_logit.weight,
-                                self.vision_logit.bias, residual=region_mask)
-        linguisic_logit = F.linear(_dropout(sequence_output_t, self.dropout), self.linguisic_logit.weight,
-                                   self.linguisic_logit.bias)
+        if "vil_logit" in want:
+            vil_logit = F.linear(pooled_output, self.vil_logit.weight, self.vil_logit.bias)
+        if "vil_tri_prediction" in want:
+            vil_tri_prediction = F.linear(pooled_output, self.vil_tri_prediction.weight, self.vil_tri_prediction.bias)
+        if "vision_logit" not in want:
+            _skip_dropout_seed(self.dropout)
+        elif on16:
+            # one launch over the bf16 regions: dropout, the 1-wide linear and the additive region mask
+            vision_logit = F.skinny_linear(sequence_output_v, self.vision_logit.weight, self.vision_logit.bias,
+                                           row_add=ops.additive_mask(image_attention_mask), drop_p=_drop_p(self.dropout))
+        else:
+            # like the reference this needs image_attention_mask (:1692-1694 crash on None)
+            region_mask = ops.additive_mask(image_attention_mask).unsqueeze(2)
+            vision_logit = F.linear(_dropout(sequence_output_v, self.dropout), self.vision_logit.weight,
+                                    self.vision_logit.bias, residual=region_mask)
+        if "linguisic_logit" not in want:
+            _skip_dropout_seed(self.dropout)
+        elif on16:
+            linguisic_logit = F.skinny_linear(sequence_output_t, self.linguisic_logit.weight, self.linguisic_logit.bias,
+                                              drop_p=_drop_p(self.dropout))
+        else:
+            linguisic_logit = F.linear(_dropout(sequence_output_t, self.dropout), self.linguisic_logit.weight,
+                                       self.linguisic_logit.bias)
         return (vil_prediction, vil_prediction_gqa, vil_logit, vil_binary_prediction, vil_tri_prediction,
                 vision_prediction, vision_logit, linguisic_prediction, linguisic_logit, all_attention_mask)
