@@ -108,8 +108,17 @@ def _map_for(M, src_rows, seed):
 @pytest.mark.parametrize("M", [1, 33, 96])
 @pytest.mark.parametrize("cols", [8, 256, 1024])
 def test_gather_and_scatter_move_rows_bit_for_bit(M, cols):
+    _check_gather_and_scatter(M, cols, lds=cols + 16, ldo=cols + 8, ldf=cols + 24)
+
+
+def test_gather_and_scatter_move_dense_rows_bit_for_bit():
+    """lds == ldo == cols: the form the fp32 block rows take through the same mover (csrc/rowmap.hip)"""
+    _check_gather_and_scatter(33, 8, lds=8, ldo=8, ldf=8)
+
+
+def _check_gather_and_scatter(M, cols, lds, ldo, ldf):
     lib = _lib()
-    src_rows, lds, ldo = 50, cols + 16, cols + 8
+    src_rows = 50
     bits = _random_bf16_bits(src_rows, lds, seed=M * 7 + cols)
     src = torch.from_numpy(bits.view(np.int16)).to(DEV)
     m = _map_for(M, src_rows, seed=M + cols)
@@ -126,7 +135,6 @@ def test_gather_and_scatter_move_rows_bit_for_bit(M, cols):
     assert (got[inside, :cols].view(np.int16) == sel.numpy()).all()
 
     # scatter: every row of `full` is its compact row or +0 - written once, no fill in front (the buffer starts as NaN)
-    ldf = cols + 24
     inv = Guard(src_rows, torch.int32)
     full = Guard(src_rows * ldf, BF16, fill16=NAN16)
     compact = torch.from_numpy(got.view(np.int16).copy()).to(DEV)        # the gathered block, row stride ldo
@@ -221,7 +229,7 @@ def _loss_case(rows, n, seed):
     return buf.to(DEV), ld, labels.to(DEV)
 
 
-@pytest.mark.parametrize("rows", [1, 5, 70])
+@pytest.mark.parametrize("rows", [1, 5, 64, 65, 70])      # 64, 65: exactly one row tile, one tile + a single row
 @pytest.mark.parametrize("n", [2, 211, 1601])
 def test_cross_entropy_backward_emits_the_cast_of_the_fp32_gradient_and_its_transpose(rows, n):
     from vilbert import ops

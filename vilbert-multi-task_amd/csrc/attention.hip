@@ -28,6 +28,7 @@
 // Dropout masks are regenerated from (seed, element index) - see rng.h.
 #include "common.h"
 #include "rng.h"
+#include "row_kit.h"
 
 namespace {
 
@@ -38,11 +39,7 @@ namespace {
 // statistics (mask, lse, D vector and the optional probabilities stay fp32 tensors).
 #ifdef VB_ATTN_BF16
 typedef unsigned short io_t;
-__device__ __forceinline__ f32x4 ld4(const io_t* p) {
-    const uint2 w = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
-                 __uint_as_float(w.y & 0xffff0000u)};
-}
+__device__ __forceinline__ f32x4 ld4(const io_t* p) { return bf16_unpack4(*reinterpret_cast<const uint2*>(p)); }
 __device__ __forceinline__ float ld1(const io_t* p) { return __uint_as_float((unsigned)*p << 16); }
 __device__ __forceinline__ void st1(io_t* p, float v) { *p = (io_t)vb_bf16_round(v); }
 // one output row piece: element a[dt][r] belongs to column 16 dt + c of the row; `op` already points at column c. Lanes c and

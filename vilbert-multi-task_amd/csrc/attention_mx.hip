@@ -20,12 +20,12 @@
 //            head; head_dim 64: half a word).
 #include "common.h"
 #include "mx8.h"
+#include "row_kit.h"
 
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 struct AttnMxP {
     int batch, heads, n_q, n_k, n_qt, n_kt;

@@ -2,25 +2,19 @@
 // bf16 shadows (row-major AND transposed) of the fp32 master weights, refreshed once per optimizer step, and the column
 // sums of a bf16 matrix (bias gradient). Called directly by tests/test_bf16_helpers_gpu.py.
 #include "common.h"
+#include "row_kit.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ unsigned short bf16_rne(float v) { return (unsigned short)vb_bf16_round(v); }
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return vb_bf16_pack(lo, hi); }
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(long n8, const float* __restrict__ x, unsigned short* __restrict__ y,
                                                             long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n8) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(x + 8 * i), c = *reinterpret_cast<const f32x4*>(x + 8 * i + 4);
-        *reinterpret_cast<v4i*>(y + 8 * i) = v4i{(int)pack_bf16(a[0], a[1]), (int)pack_bf16(a[2], a[3]), (int)pack_bf16(c[0], c[1]),
-                                                 (int)pack_bf16(c[2], c[3])};
+        float f[8];
+        load8(x + 8 * i, f);
+        *reinterpret_cast<v4i*>(y + 8 * i) = pack8(f);
     } else if (i == n8) {
-        for (long e = 8 * n8; e < n; ++e) y[e] = bf16_rne(x[e]);
+        for (long e = 8 * n8; e < n; ++e) y[e] = (unsigned short)vb_bf16_round(x[e]);
     }
 }
 
@@ -33,20 +27,9 @@ __global__ __launch_bounds__(256) void cast_rows_f32_bf16_kernel(long rows, int 
     if (i >= rows * chunks) return;
     const long r = i / chunks;
     const int c = (int)(i % chunks) * 8;
-    const float* __restrict__ xp = x + r * ldx + c;
-    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
-    if (c + 8 <= n) {
-        a = *reinterpret_cast<const f32x4*>(xp);
-        b = *reinterpret_cast<const f32x4*>(xp + 4);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (c + e < n) a[e] = xp[e];
-            if (c + 4 + e < n) b[e] = xp[4 + e];
-        }
-    }
-    *reinterpret_cast<v4i*>(y + r * ldy + c) = v4i{(int)pack_bf16(a[0], a[1]), (int)pack_bf16(a[2], a[3]), (int)pack_bf16(b[0], b[1]),
-                                                   (int)pack_bf16(b[2], b[3])};
+    float f[8];
+    load8(x + r * ldx + c, c, n, true, f);
+    *reinterpret_cast<v4i*>(y + r * ldy + c) = pack8(f);
 }
 
 __global__ __launch_bounds__(256) void cast_bf16_f32_kernel(long n8, const unsigned short* __restrict__ x, float* __restrict__ y,
@@ -54,26 +37,25 @@ __global__ __launch_bounds__(256) void cast_bf16_f32_kernel(long n8, const unsig
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i < n8) {
         const v4i w = *reinterpret_cast<const v4i*>(x + 8 * i);
-        *reinterpret_cast<f32x4*>(y + 8 * i) = f32x4{bf16_lo(w[0]), bf16_hi(w[0]), bf16_lo(w[1]), bf16_hi(w[1])};
-        *reinterpret_cast<f32x4*>(y + 8 * i + 4) = f32x4{bf16_lo(w[2]), bf16_hi(w[2]), bf16_lo(w[3]), bf16_hi(w[3])};
+        *reinterpret_cast<f32x4*>(y + 8 * i) = bf16_unpack4(uint2{(unsigned)w[0], (unsigned)w[1]});
+        *reinterpret_cast<f32x4*>(y + 8 * i + 4) = bf16_unpack4(uint2{(unsigned)w[2], (unsigned)w[3]});
     } else if (i == n8) {
-        for (long e = 8 * n8; e < n; ++e) y[e] = __uint_as_float((unsigned)x[e] << 16);
+        for (long e = 8 * n8; e < n; ++e) y[e] = bf16_lo(x[e]);
     }
 }
 
-// fp32 master weight [rows, cols] -> bf16 shadow rows (w16 [rows, ld16]) AND its transpose (wt16 [cols, ldt], written at
-// column offset col_off = the row offset of this segment inside a stacked weight); 64 x 64 tiles through LDS
-__global__ __launch_bounds__(256) void weight_shadow_kernel(int rows, int cols, const float* __restrict__ w, long ldw,
-                                                            unsigned short* __restrict__ w16, long ld16,
-                                                            unsigned short* __restrict__ wt16, long ldt) {
+// One 64 x 64 tile at (r0, c0) of an fp32 master weight -> its bf16 shadow rows (w16, row stride ld16; may be null) AND their
+// transpose (wt16, row stride ldt; may be null) through LDS. 256 threads: thread t owns 4 columns of the rows t / 16 + 16 i.
+__device__ __forceinline__ void shadow_tile(int r0, int c0, const float* __restrict__ w, long ldw,
+                                            unsigned short* __restrict__ w16, long ld16, unsigned short* __restrict__ wt16,
+                                            long ldt) {
     __shared__ unsigned short tile[64][66];
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     const int tr = threadIdx.x >> 4, tc = (threadIdx.x & 15) * 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int row = tr + 16 * i;
         const f32x4 v = *reinterpret_cast<const f32x4*>(w + (long)(r0 + row) * ldw + c0 + tc);
-        const unsigned lo = pack_bf16(v[0], v[1]), hi = pack_bf16(v[2], v[3]);
+        const unsigned lo = vb_bf16_pack(v[0], v[1]), hi = vb_bf16_pack(v[2], v[3]);
         if (w16 != nullptr) *reinterpret_cast<uint2*>(w16 + (long)(r0 + row) * ld16 + c0 + tc) = uint2{lo, hi};
         tile[row][tc] = (unsigned short)lo; tile[row][tc + 1] = (unsigned short)(lo >> 16);
         tile[row][tc + 2] = (unsigned short)hi; tile[row][tc + 3] = (unsigned short)(hi >> 16);
@@ -89,10 +71,16 @@ __global__ __launch_bounds__(256) void weight_shadow_kernel(int rows, int cols, 
     }
 }
 
+// fp32 master weight [rows, cols] -> bf16 shadow rows (w16 [rows, ld16]) AND its transpose (wt16 [cols, ldt], written at
+// column offset col_off = the row offset of this segment inside a stacked weight); grid (cols / 64, rows / 64)
+__global__ __launch_bounds__(256) void weight_shadow_kernel(const float* __restrict__ w, long ldw, unsigned short* __restrict__ w16,
+                                                            long ld16, unsigned short* __restrict__ wt16, long ldt) {
+    shadow_tile(blockIdx.y * 64, blockIdx.x * 64, w, ldw, w16, ld16, wt16, ldt);
+}
+
 // the same for EVERY registered weight in one launch (once per optimizer step): block b finds its segment in the table by
 // bisection over the segments' first tile
 __global__ __launch_bounds__(256) void weight_shadow_multi_kernel(int n_segs, const vb_shadow_seg* __restrict__ tab) {
-    __shared__ unsigned short tile[64][66];
     int lo = 0, hi = n_segs - 1;
     const long b = blockIdx.x;
     while (lo < hi) {
@@ -101,25 +89,7 @@ __global__ __launch_bounds__(256) void weight_shadow_multi_kernel(int n_segs, co
     }
     const vb_shadow_seg sg = tab[lo];
     const int t = (int)(b - sg.tile0), tiles_c = sg.cols >> 6;
-    const int r0 = (t / tiles_c) * 64, c0 = (t % tiles_c) * 64;
-    const int tr = threadIdx.x >> 4, tc = (threadIdx.x & 15) * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = tr + 16 * i;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(sg.w + (long)(r0 + row) * sg.cols + c0 + tc);
-        const unsigned lo2 = pack_bf16(v[0], v[1]), hi2 = pack_bf16(v[2], v[3]);
-        *reinterpret_cast<uint2*>(sg.w16 + (long)(r0 + row) * sg.ld16 + c0 + tc) = uint2{lo2, hi2};
-        tile[row][tc] = (unsigned short)lo2; tile[row][tc + 1] = (unsigned short)(lo2 >> 16);
-        tile[row][tc + 2] = (unsigned short)hi2; tile[row][tc + 3] = (unsigned short)(hi2 >> 16);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int col = tr + 16 * i;
-        const unsigned lo2 = (unsigned)tile[tc][col] | ((unsigned)tile[tc + 1][col] << 16);
-        const unsigned hi2 = (unsigned)tile[tc + 2][col] | ((unsigned)tile[tc + 3][col] << 16);
-        *reinterpret_cast<uint2*>(sg.wt16 + (long)(c0 + col) * sg.ldt + r0 + tc) = uint2{lo2, hi2};
-    }
+    shadow_tile((t / tiles_c) * 64, (t % tiles_c) * 64, sg.w, sg.cols, sg.w16, sg.ld16, sg.wt16, sg.ldt);
 }
 
 // column sums of a bf16 [rows, cols] matrix (bias gradient): stage 1 - a block owns 256 columns x one row slab, a thread 4
@@ -137,7 +107,7 @@ __global__ __launch_bounds__(256) void colsum16_kernel(long rows, int cols, cons
     if (col < cols)
         for (long r = lo + wave; r < hi; r += 4) {
             const uint2 w = *reinterpret_cast<const uint2*>(x + r * ldx + col);
-            s += f32x4{bf16_lo(w.x), bf16_hi(w.x), bf16_lo(w.y), bf16_hi(w.y)};
+            s += bf16_unpack4(w);
         }
     if (wave > 0) red[wave - 1][lane] = s;
     __syncthreads();
@@ -146,15 +116,24 @@ __global__ __launch_bounds__(256) void colsum16_kernel(long rows, int cols, cons
         *reinterpret_cast<f32x4*>(part + (long)blockIdx.y * cols + col) = s;
     }
 }
-__global__ __launch_bounds__(256) void colsum16_finish_kernel(int cols, const float* __restrict__ part, float* __restrict__ out) {
-    const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= cols) return;
-    float s = 0.f;
-    for (int i = 0; i < CS_SLABS; ++i) s += part[(long)i * cols + c];
-    out[c] += s;
+// out[j] += part[0][j] + part[1][j] + ... in that order, j < n: stage 2 here, and the per-64-rows partial sums the loss
+// backward and the cast of heads16.hip leave behind (vbh_colsum_parts)
+__global__ __launch_bounds__(256) void colsum_finish_kernel(long parts, int n, const float* __restrict__ part, long ldp,
+                                                            float* __restrict__ out) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    float a = 0.f;
+    for (long p = 0; p < parts; ++p) a += part[p * ldp + j];
+    out[j] += a;
 }
 
 }  // namespace
+
+int vbrows::colsum_finish(hipStream_t st, long parts, int n, const float* part, long ldp, float* out) {
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, parts, n, part, ldp, out);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int vb_cast_f32_bf16(void* stream, int64_t n, const float* x, uint16_t* y) {
     if (x == nullptr || y == nullptr || n <= 0) return VB_E_BADARG;
@@ -168,7 +147,7 @@ extern "C" int vb_cast_f32_bf16(void* stream, int64_t n, const float* x, uint16_
 
 extern "C" int vb_cast_rows_f32_bf16(void* stream, int64_t rows, int32_t n, const float* x, int64_t ldx, uint16_t* y, int64_t ldy) {
     if (x == nullptr || y == nullptr || rows <= 0 || n <= 0 || ldx < n || ldy < n) return VB_E_BADARG;
-    if (ldx % 4 != 0 || ldy % 8 != 0 || !vb_aligned16(x) || !vb_aligned16(y)) return VB_E_ALIGN;
+    if (!vb_row32_ok(x, ldx) || !vb_row16_ok(y, ldy)) return VB_E_ALIGN;
     const long work = rows * (ldy / 8);
     hipLaunchKernelGGL(cast_rows_f32_bf16_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        (long)rows, (int)n, x, (long)ldx, y, (long)ldy);
@@ -192,8 +171,8 @@ extern "C" int vb_weight_shadow_bf16(void* stream, int32_t rows, int32_t cols, c
     if (rows % 64 != 0 || cols % 64 != 0 || ldw % 4 != 0 || !vb_aligned16(w)) return VB_E_ALIGN;
     if (w16 != nullptr && (ld16 % 4 != 0 || ld16 < cols || (reinterpret_cast<uintptr_t>(w16) & 7u) != 0)) return VB_E_ALIGN;
     if (wt16 != nullptr && (ldt % 4 != 0 || ldt < rows || (reinterpret_cast<uintptr_t>(wt16) & 7u) != 0)) return VB_E_ALIGN;
-    hipLaunchKernelGGL(weight_shadow_kernel, dim3(cols / 64, rows / 64), dim3(256), 0, static_cast<hipStream_t>(stream), rows, cols,
-                       w, (long)ldw, w16, (long)ld16, wt16, (long)ldt);
+    hipLaunchKernelGGL(weight_shadow_kernel, dim3(cols / 64, rows / 64), dim3(256), 0, static_cast<hipStream_t>(stream), w,
+                       (long)ldw, w16, (long)ld16, wt16, (long)ldt);
     VB_LAUNCH_CHECK();
     return 0;
 }
@@ -216,7 +195,5 @@ extern "C" int vb_colsum_bf16(void* stream, int64_t rows, int32_t cols, const ui
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(colsum16_kernel, dim3((cols + 255) / 256, CS_SLABS), dim3(256), 0, st, (long)rows, cols, x, (long)ldx, workspace);
     VB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(colsum16_finish_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, cols, workspace, out);
-    VB_LAUNCH_CHECK();
-    return 0;
+    return vbrows::colsum_finish(st, CS_SLABS, cols, workspace, cols, out);
 }

@@ -5,6 +5,7 @@
 
 #include "bf16_round.h"  // host-only part: the one fp32 -> bf16 rounding (NaN-safe) of every bf16 store
 #include "gemm_plan.h"   // host-only part: the C ABI header, vb_aligned16, vb_env_int / vb_env_float
+#include "row_checks.h"  // host-only part: extent / alignment checks and grid sizes of the row kernels
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -37,8 +38,14 @@ int drop_add(hipStream_t st, long M, int cols, const float* lin, const float* re
              long src_rows, float* out, float p, uint64_t seed);
 // inv[R] = the compact row with map[r] == R (the first, should there be more), or -1
 int invert(hipStream_t st, long src_rows, long M, const int32_t* map, int32_t* inv);
-// full[R] = compact[inv[R]], zeros where inv[R] < 0
-int scatter(hipStream_t st, long src_rows, int cols, const float* compact, const int32_t* inv, float* full);
+// full[R] = compact[inv[R]] (compact: M rows), zeros where inv[R] is outside [0, M)
+int scatter(hipStream_t st, long src_rows, int cols, const float* compact, long M, const int32_t* inv, float* full);
+// the mover behind gather and scatter, of any element type: out[r] = src[map[r]] for r < rows in 16-byte chunks, zeros where
+// map[r] is outside [0, src_rows); `chunks` per row, the row strides lds / ldo in 16-byte units, at most max_blocks blocks
+int move_rows(hipStream_t st, long rows, int chunks, const void* src, long lds, long src_rows, const int32_t* map, void* out,
+              long ldo, long max_blocks);
+// out[j] += part[0][j] + part[1][j] + ... + part[parts - 1][j] in that order, j < n (bf16_helpers.hip)
+int colsum_finish(hipStream_t st, long parts, int n, const float* part, long ldp, float* out);
 }  // namespace vbrows
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -40,12 +40,7 @@ __global__ __launch_bounds__(256) void dropout_kernel(long n, const float* __res
     }
 }
 
-inline unsigned grid_for(long work_items) {
-    long blocks = (work_items + 255) / 256;
-    if (blocks > 2048) blocks = 2048;  // ~8 blocks per CU, grid-stride the rest
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
+constexpr long EW_MAX_BLOCKS = 2048;   // ~8 blocks per CU, grid-stride the rest
 
 }  // namespace
 
@@ -55,15 +50,15 @@ extern "C" int vb_act_bwd(void* stream, int64_t n, int32_t act, const float* dy,
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long n4 = n / 4;
     if (act == VB_ACT_GELU)
-        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_GELU>, dim3(grid_for(n4)), dim3(256), 0, st, n4,
+        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_GELU>, dim3(vb_grid_for(n4, 256, EW_MAX_BLOCKS)), dim3(256), 0, st, n4,
                            reinterpret_cast<const f32x4*>(dy), reinterpret_cast<const f32x4*>(preact),
                            reinterpret_cast<f32x4*>(dx));
     else if (act == VB_ACT_RELU)
-        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_RELU>, dim3(grid_for(n4)), dim3(256), 0, st, n4,
+        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_RELU>, dim3(vb_grid_for(n4, 256, EW_MAX_BLOCKS)), dim3(256), 0, st, n4,
                            reinterpret_cast<const f32x4*>(dy), reinterpret_cast<const f32x4*>(preact),
                            reinterpret_cast<f32x4*>(dx));
     else if (act == VB_ACT_SWISH)
-        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_SWISH>, dim3(grid_for(n4)), dim3(256), 0, st, n4,
+        hipLaunchKernelGGL(act_bwd_kernel<VB_ACT_SWISH>, dim3(vb_grid_for(n4, 256, EW_MAX_BLOCKS)), dim3(256), 0, st, n4,
                            reinterpret_cast<const f32x4*>(dy), reinterpret_cast<const f32x4*>(preact),
                            reinterpret_cast<f32x4*>(dx));
     else
@@ -77,7 +72,7 @@ extern "C" int vb_dropout(void* stream, int64_t n, const float* x, const float* 
     if (x == nullptr || y == nullptr || n <= 0 || !(p >= 0.f && p < 1.f)) return VB_E_BADARG;
     if (!vb_aligned16(x) || !vb_aligned16(y) || (residual != nullptr && !vb_aligned16(residual))) return VB_E_ALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, st, (long)n, x, residual, y, p,
+    hipLaunchKernelGGL(dropout_kernel, dim3(vb_grid_for(n / 4 + 1, 256, EW_MAX_BLOCKS)), dim3(256), 0, st, (long)n, x, residual, y, p,
                        1.0f / (1.0f - p), seed, vb_seed_epoch());
     VB_LAUNCH_CHECK();
     return 0;

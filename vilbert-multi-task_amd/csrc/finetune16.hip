@@ -14,12 +14,11 @@
 // in memory. No atomics, nothing allocated.
 #include "common.h"
 #include "rng.h"
+#include "row_kit.h"
 
 #include "../../include/vilbert_hip_finetune.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int F_WAVE = 64;
 constexpr int F_THREADS = 256;             // forward / input gradient: 4 waves = 4 rows in flight per block
@@ -29,27 +28,12 @@ constexpr long F_PART_ROWS = 32;           // weight gradient: rows per partial 
 constexpr long F_MAX_PARTS = 512;          // ... until this many partial rows, then longer ranges
 constexpr int F_RED_COLS = 64;             // stage 2: columns per block, F_THREADS / F_RED_COLS interleaved slices of the parts
 constexpr int F_RED_SLICES = F_THREADS / F_RED_COLS;
-constexpr int F_TILE = 64;                 // rows and columns of a tile of the cast with column sums
+constexpr int F_TILE = KIT_TILE;           // rows and columns of a tile of the cast with column sums (row_kit.h)
 constexpr long F_MAX_TILED = 1L << 21;     // widths / row counts whose 64-wide tiles still fit a grid dimension
 
-inline bool extent_ok(int64_t a, int64_t b) { return a <= 0 || b <= INT64_MAX / a; }
 inline long parts_for(long rows) {
     const long p = (rows + F_PART_ROWS - 1) / F_PART_ROWS;
     return p > F_MAX_PARTS ? F_MAX_PARTS : p;
-}
-
-// the 8 bf16 values of a 16-byte chunk as fp32 (exact)
-__device__ __forceinline__ void unpack8(v4i v, float* f) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        f[2 * k] = __uint_as_float((unsigned)v[k] << 16);
-        f[2 * k + 1] = __uint_as_float((unsigned)v[k] & 0xffff0000u);
-    }
-}
-
-__device__ __forceinline__ v4i pack8(const float* v) {
-    return v4i{(int)vb_bf16_pack(v[0], v[1]), (int)vb_bf16_pack(v[2], v[3]), (int)vb_bf16_pack(v[4], v[5]),
-               (int)vb_bf16_pack(v[6], v[7])};
 }
 
 // lane's chunks of the NN weight rows: w[j][i][e] = w[j, (lane + 64 i) * 8 + e]
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(F_THREADS) void skinny_fwd_kernel(long rows, int K8
             const int c = lane + F_WAVE * i;
             if (c < K8) {
                 float f[8];
-                unpack8(*reinterpret_cast<const v4i*>(xr + (long)c * 8), f);
+                bf16_unpack8(*reinterpret_cast<const v4i*>(xr + (long)c * 8), f);
                 if (drop) drop8(f, seed, (uint64_t)(r * K + (long)c * 8), p, scale);
 #pragma unroll
                 for (int j = 0; j < NN; ++j)
@@ -188,7 +172,7 @@ __global__ __launch_bounds__(F_WAVE) void skinny_wgrad_kernel(long rows, long rp
             const int c = lane + F_WAVE * i;
             if (c < K8) {
                 float f[8];
-                unpack8(*reinterpret_cast<const v4i*>(xr + (long)c * 8), f);
+                bf16_unpack8(*reinterpret_cast<const v4i*>(xr + (long)c * 8), f);
                 if (drop) drop8(f, seed, (uint64_t)(r * K + (long)c * 8), p, scale);
 #pragma unroll
                 for (int j = 0; j < NN; ++j)
@@ -241,54 +225,23 @@ __global__ __launch_bounds__(F_THREADS) void skinny_wgrad_reduce_kernel(long par
     }
 }
 
-// fp32 rows -> bf16 rows padded with zero columns to n_pad, and per 64 rows the fp32 column sums of the UNROUNDED values:
-// grid (ceil(rows / 64), n_pad / 64), thread t owns the 8 columns (t & 7) * 8 .. of the rows t >> 3 and (t >> 3) + 32 of its tile
-__global__ __launch_bounds__(F_THREADS) void cast_rows_colsum_kernel(long rows, int n, const float* __restrict__ x, long ldx,
-                                                                     unsigned short* __restrict__ G, long ldg,
-                                                                     float* __restrict__ colsum_part, long n_pad) {
-    __shared__ float colred[32][F_TILE + 1];
-    const int tr = threadIdx.x >> 3, tc = (threadIdx.x & 7) * 8;
-    const long r0 = (long)blockIdx.x * F_TILE;
-    const int c0 = blockIdx.y * F_TILE, c = c0 + tc;
-    float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const long r = r0 + tr + 32 * i;
-        if (r >= rows) continue;
-        float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const float* q = x + r * ldx + c;
-        if (c + 8 <= n) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(q), b = *reinterpret_cast<const f32x4*>(q + 4);
-            f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e)
-                if (c + e < n) f[e] = q[e];
-        }
-        *reinterpret_cast<v4i*>(G + r * ldg + c) = pack8(f);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) cs[e] += f[e];
+// fp32 rows -> bf16 rows padded with zero columns to n_pad, and per 64 rows the fp32 column sums of the UNROUNDED values: the
+// identity as the producer of tile_rows16_kernel (row_kit.h), grid (ceil(rows / 64), n_pad / 64)
+struct CastRows {
+    static constexpr bool TRANSPOSE = false;
+    const float* x; long ldx;
+    __device__ float scale() const { return 1.f; }
+    __device__ bool operator()(long r, int c, int n, float, float (&f)[8]) const {
+        load8(x + r * ldx + c, c, n, true, f);
+        return true;
     }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) colred[tr][tc + e] = cs[e];
-    __syncthreads();
-    if (threadIdx.x < F_TILE) {                                  // rows in a fixed order: the same bits on every run
-        float a = 0.f;
-#pragma unroll 8
-        for (int k = 0; k < 32; ++k) a += colred[k][threadIdx.x];
-        colsum_part[(long)blockIdx.x * n_pad + c0 + threadIdx.x] = a;
-    }
-}
+};
 
 // Forward / input gradient: every wave loads the n x K fp32 weight once (from L2) and then streams its rows, so with two rows per
 // wave the weight is ~25 % extra L2 traffic at n = 1 (4 KB per 2 x 2 KB of x at K = 1,024) - the price of ~6 blocks per CU at
 // 12,928 rows; more rows per wave trades that against fewer waves in flight (not tried on the GPU). The weight gradient's stage 1
 // runs one wave per 32 rows: ~404 waves on 256 CUs at that row count, each writing n K + 4 partial floats.
-inline unsigned row_grid(long rows) {
-    long blocks = (rows + 2 * F_WAVES - 1) / (2 * F_WAVES);      // two rows per wave until the grid is full
-    if (blocks > F_MAX_BLOCKS) blocks = F_MAX_BLOCKS;
-    return (unsigned)(blocks < 1 ? 1 : blocks);
-}
+constexpr int F_ROWS_PER_BLOCK = 2 * F_WAVES;      // two rows per wave until the grid is full (F_MAX_BLOCKS)
 
 // the checks every entry point shares: (rows, K, n), the bf16 tensor [rows, K] (stride ld16), the weight-shaped fp32 tensor
 // [n, K] (stride ld32), the fp32 [rows, n] tensor (stride ldn)
@@ -297,9 +250,8 @@ int check_common(int64_t rows, int32_t K, int32_t n, const void* p16, int64_t ld
     if (!p16 || !p32 || !pn) return VB_E_BADARG;
     if (rows < 0 || n < 1 || n > VBF_MAX_N || K < 8 || ld16 < K || ld32 < K || ldn < n) return VB_E_BADARG;
     if (!(p >= 0.f && p < 1.f)) return VB_E_BADARG;
-    if (K % 8 != 0 || ld16 % 8 != 0 || ld32 % 4 != 0 || !vb_aligned16(p16) || !vb_aligned16(p32) || !vb_aligned16(pn))
-        return VB_E_ALIGN;
-    if (K > VBF_MAX_K || rows > INT32_MAX || !extent_ok(rows, ld16) || !extent_ok(rows, ldn)) return VB_E_RANGE;
+    if (K % 8 != 0 || !vb_row16_ok(p16, ld16) || !vb_row32_ok(p32, ld32) || !vb_aligned16(pn)) return VB_E_ALIGN;
+    if (K > VBF_MAX_K || rows > INT32_MAX || !vb_extent_ok(rows, ld16) || !vb_extent_ok(rows, ldn)) return VB_E_RANGE;
     return 0;
 }
 
@@ -329,7 +281,8 @@ extern "C" int vbf_skinny_linear_fwd(void* stream, int64_t rows, int32_t K, int3
     if (!vb_aligned16(bias) || !vb_aligned16(row_add)) return VB_E_ALIGN;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    VBF_DISPATCH(skinny_fwd_kernel, dim3(row_grid(rows)), dim3(F_THREADS), (long)rows, (int)(K / 8), x, (long)ldx, w, (long)ldw,
+    const dim3 grid(vb_grid_for(rows, F_ROWS_PER_BLOCK, F_MAX_BLOCKS));
+    VBF_DISPATCH(skinny_fwd_kernel, grid, dim3(F_THREADS), (long)rows, (int)(K / 8), x, (long)ldx, w, (long)ldw,
                  bias, row_add, out, (long)ldo, p, 1.0f / (1.0f - p), seed, p > 0.f ? vb_seed_epoch() : nullptr)
     VB_LAUNCH_CHECK();
     return 0;
@@ -341,7 +294,8 @@ extern "C" int vbf_skinny_linear_bwd_input(void* stream, int64_t rows, int32_t K
     if (bad) return bad;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    VBF_DISPATCH(skinny_dgrad_kernel, dim3(row_grid(rows)), dim3(F_THREADS), (long)rows, (int)(K / 8), dy, (long)ldy, w, (long)ldw,
+    const dim3 grid(vb_grid_for(rows, F_ROWS_PER_BLOCK, F_MAX_BLOCKS));
+    VBF_DISPATCH(skinny_dgrad_kernel, grid, dim3(F_THREADS), (long)rows, (int)(K / 8), dy, (long)ldy, w, (long)ldw,
                  dx, (long)lddx, p, 1.0f / (1.0f - p), seed, p > 0.f ? vb_seed_epoch() : nullptr)
     VB_LAUNCH_CHECK();
     return 0;
@@ -376,13 +330,14 @@ extern "C" int vbf_skinny_linear_bwd_weight(void* stream, int64_t rows, int32_t 
 
 extern "C" int vbf_cast_rows_colsum(void* stream, int64_t rows, int32_t n, const float* x, int64_t ldx, uint16_t* G, int64_t ldg,
                                     float* colsum_part) {
-    const long n_pad = n <= 0 ? 0 : ((long)n + 255) / 256 * 256;
+    const long n_pad = vb_padded256(n);
     if (!x || !G || !colsum_part || rows < 0 || n < 1 || ldx < n || ldg < n_pad) return VB_E_BADARG;
-    if (ldx % 4 != 0 || ldg % 8 != 0 || !vb_aligned16(x) || !vb_aligned16(G) || !vb_aligned16(colsum_part)) return VB_E_ALIGN;
-    if (rows > F_MAX_TILED || n > F_MAX_TILED || !extent_ok(rows, ldx) || !extent_ok(rows, ldg)) return VB_E_RANGE;
+    if (!vb_row32_ok(x, ldx) || !vb_row16_ok(G, ldg) || !vb_aligned16(colsum_part)) return VB_E_ALIGN;
+    if (rows > F_MAX_TILED || n > F_MAX_TILED || !vb_extent_ok(rows, ldx) || !vb_extent_ok(rows, ldg)) return VB_E_RANGE;
     if (rows == 0) return 0;
-    hipLaunchKernelGGL(cast_rows_colsum_kernel, dim3((unsigned)((rows + F_TILE - 1) / F_TILE), (unsigned)(n_pad / F_TILE)),
-                       dim3(F_THREADS), 0, (hipStream_t)stream, (long)rows, (int)n, x, (long)ldx, G, (long)ldg, colsum_part, n_pad);
+    hipLaunchKernelGGL(tile_rows16_kernel<CastRows>, dim3((unsigned)((rows + F_TILE - 1) / F_TILE), (unsigned)(n_pad / F_TILE)),
+                       dim3(F_THREADS), 0, (hipStream_t)stream, (long)rows, (int)n, CastRows{x, (long)ldx}, G, (long)ldg,
+                       (unsigned short*)nullptr, 0L, colsum_part, n_pad);
     VB_LAUNCH_CHECK();
     return 0;
 }

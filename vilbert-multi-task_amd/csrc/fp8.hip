@@ -12,6 +12,7 @@
 // The operands live in HBM as bytes: a K-contiguous [rows][K] e4m3 matrix per operand (4x less operand traffic than
 // fp32), K a multiple of 128.
 #include "gemm_core.h"
+#include "row_kit.h"
 #include <type_traits>
 
 namespace {
@@ -19,7 +20,6 @@ namespace {
 using namespace vbgemm;
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr float E4M3_MAX = 448.0f;
 

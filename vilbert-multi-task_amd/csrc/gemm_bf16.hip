@@ -23,6 +23,7 @@
 #include "gemm_bf16_plan.h"
 #include "gemm_core.h"
 #include "persistent_map.h"
+#include "row_kit.h"
 #include <type_traits>
 
 namespace {
@@ -30,7 +31,6 @@ namespace {
 using namespace vbgemm;
 using namespace vbdet;
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
@@ -60,10 +60,6 @@ struct HbCfg {
 };
 using HbFull = HbCfg<256, 3, 2>;
 using HbHalf = HbCfg<128, 2, 1>;
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) { return vb_bf16_pack(lo, hi); }
-__device__ __forceinline__ float bf16_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
 
 template <int N>
 __device__ __forceinline__ void hb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -329,13 +325,13 @@ __global__ __launch_bounds__(Cfg::THREADS, Cfg::PER_CU == 1 ? 1 : 3) void gemm_b
                         v[e] = x;
                     }
                     if (EPI == HB_RES || EPI == HB_DROPRES)
-                        v += f32x4{bf16_lo(rq[q].x), bf16_hi(rq[q].x), bf16_lo(rq[q].y), bf16_hi(rq[q].y)};
-                    if (EPI == HB_MUL) v *= f32x4{bf16_lo(rq[q].x), bf16_hi(rq[q].x), bf16_lo(rq[q].y), bf16_hi(rq[q].y)};
+                        v += bf16_unpack4(rq[q]);
+                    if (EPI == HB_MUL) v *= bf16_unpack4(rq[q]);
                     if (OUT == HB_OUT_F32) {
                         if (live) *reinterpret_cast<f32x4*>(p.C32 + (long)m * p.ldc32 + nb + 8 * q + 4 * hi) = v;
                     } else {
-                        o2[q] = uint2{pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3])};
-                        if (EPI == HB_GELU) d2[q] = uint2{pack_bf16(d[0], d[1]), pack_bf16(d[2], d[3])};
+                        o2[q] = uint2{vb_bf16_pack(v[0], v[1]), vb_bf16_pack(v[2], v[3])};
+                        if (EPI == HB_GELU) d2[q] = uint2{vb_bf16_pack(d[0], d[1]), vb_bf16_pack(d[2], d[3])};
                     }
                 }
                 if (OUT == HB_OUT_BF16) {

@@ -358,8 +358,8 @@ int ffn_block_rows_bwd(void* st, WgradQueue& wq, const vb_ffn_block& f) {
     wq.push(M, f.o, dod, f.ctx_rows);
     // what the attention block reads, at full size
     VB_TRY(vbrows::invert(hs, R, M, f.row_map, inv));
-    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.d_sum1), inv, static_cast<float*>(f.d_sum1_full)));
-    return vbrows::scatter(hs, R, f.Hc, compact(f.d_ctx), inv, static_cast<float*>(f.d_ctx_full));
+    VB_TRY(vbrows::scatter(hs, R, f.H, compact(f.d_sum1), M, inv, static_cast<float*>(f.d_sum1_full)));
+    return vbrows::scatter(hs, R, f.Hc, compact(f.d_ctx), M, inv, static_cast<float*>(f.d_ctx_full));
 }
 
 template <bool B16>

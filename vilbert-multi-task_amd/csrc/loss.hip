@@ -3,39 +3,25 @@
 //    on the masked-LM logits [rows, 30522] and the alignment logits [B, 2] (vilbert.py:1453,1578-1585);
 //  * KL divergence between a target distribution and log_softmax(scores), summed over the rows and divided
 //    by a caller-given count - nn.KLDivLoss(reduction="none")(log_softmax(pred), target) (:1454,1516-1522).
-// One 256-thread block per row: max, sum-exp and the label / target terms are reduced in registers + LDS;
+// One 256-thread block per row: max, sum-exp and the label / target terms are reduced in registers + LDS (row_kit.h);
 // the row (<= 122 KB) is re-read from L2, never from HBM. The softmax is never materialised in the
-// forward; the backward writes the gradient of the logits directly from the saved log-sum-exp.
+// forward; the backward writes the gradient of the logits directly from the saved log-sum-exp (row_kit.h: xent_grad, kl_grad -
+// the expressions heads16.hip rounds to bf16).
 // HBM-bound: forward reads 4 n bytes per row (KL: 8 n), backward reads 4 n (8 n) and writes 4 n.
 #include "common.h"
+#include "row_kit.h"
 
 namespace {
 
 constexpr int LOSS_THREADS = 256;
 
-__device__ __forceinline__ float block_reduce(float v, bool is_max, float* scratch) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(v, off, 64);
-        v = is_max ? fmaxf(v, o) : v + o;
-    }
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                       // scratch may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
-    __syncthreads();
-    float r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < LOSS_THREADS / 64; ++w) r = is_max ? fmaxf(r, scratch[w]) : r + scratch[w];
-    return r;
-}
-
 __device__ __forceinline__ float row_lse(const float* x, int n, float* scratch) {
     float mx = -INFINITY;
     for (int j = threadIdx.x; j < n; j += LOSS_THREADS) mx = fmaxf(mx, x[j]);
-    mx = block_reduce(mx, true, scratch);
+    mx = block_reduce<true, LOSS_THREADS>(mx, scratch);
     float s = 0.f;
     for (int j = threadIdx.x; j < n; j += LOSS_THREADS) s += expf(x[j] - mx);
-    s = block_reduce(s, false, scratch);
+    s = block_reduce<false, LOSS_THREADS>(s, scratch);
     return mx + logf(s);
 }
 
@@ -71,8 +57,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_mean_kernel(long rows, cons
         s += row_loss[r];
         if (labels != nullptr) c += labels[r] != ignore ? 1.f : 0.f;
     }
-    s = block_reduce(s, false, scratch);
-    c = labels != nullptr ? block_reduce(c, false, scratch) : (divisor_dev != nullptr ? divisor_dev[0] : divisor);
+    s = block_reduce<false, LOSS_THREADS>(s, scratch);
+    c = labels != nullptr ? block_reduce<false, LOSS_THREADS>(c, scratch) : (divisor_dev != nullptr ? divisor_dev[0] : divisor);
     if (threadIdx.x == 0) {
         loss[0] = s / c;                   // 0 / 0 = NaN when nothing is labelled, like the reference
         count_out[0] = c;
@@ -93,7 +79,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void xent_bwd_kernel(int n, const flo
     }
     const float* x = logits + r * ld;
     const float l = lse[r], g = gout[0] / count[0];
-    for (int j = threadIdx.x; j < n; j += LOSS_THREADS) d[j] = (expf(x[j] - l) - (j == lab ? 1.f : 0.f)) * g;
+    for (int j = threadIdx.x; j < n; j += LOSS_THREADS) d[j] = xent_grad(x[j], l, j == lab, g);
 }
 
 __global__ __launch_bounds__(LOSS_THREADS) void kl_fwd_kernel(int n, const float* __restrict__ scores, long ld,
@@ -112,8 +98,8 @@ __global__ __launch_bounds__(LOSS_THREADS) void kl_fwd_kernel(int n, const float
         acc += tj > 0.f ? tj * (logf(tj) - (x[j] - lse)) : -tj * (x[j] - lse);
         ts += tj;
     }
-    acc = block_reduce(acc, false, scratch);
-    ts = block_reduce(ts, false, scratch);
+    acc = block_reduce<false, LOSS_THREADS>(acc, scratch);
+    ts = block_reduce<false, LOSS_THREADS>(ts, scratch);
     if (threadIdx.x == 0) {
         row_loss[r] = acc;
         lse_out[r] = lse;
@@ -132,8 +118,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void kl_bwd_kernel(int n, const float
     const float* t = target + r * ldt;
     float* d = dscores + r * ldd;
     const float l = lse[r], ts = tsum[r], g = gout[0] / (divisor_dev != nullptr ? divisor_dev[0] : divisor);
-    // d/dx_j of -sum_k t_k (x_k - lse) = softmax_j * sum(t) - t_j
-    for (int j = threadIdx.x; j < n; j += LOSS_THREADS) d[j] = (expf(x[j] - l) * ts - t[j]) * g;
+    for (int j = threadIdx.x; j < n; j += LOSS_THREADS) d[j] = kl_grad(x[j], l, ts, t[j], g);
 }
 
 }  // namespace

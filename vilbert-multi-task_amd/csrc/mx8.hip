@@ -43,6 +43,7 @@
 #include "gemm_core.h"
 #include "mx8.h"
 #include "persistent_map.h"
+#include "row_kit.h"
 #include <type_traits>
 
 namespace {
@@ -50,15 +51,10 @@ namespace {
 using namespace vbgemm;
 
 typedef int v8i __attribute__((ext_vector_type(8)));
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // four consecutive elements of an fp32 or a bfloat16 row as f32x4
 __device__ __forceinline__ f32x4 mx_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 mx_ld4(const unsigned short* p) {
-    const uint2 t = *reinterpret_cast<const uint2*>(p);
-    return f32x4{__uint_as_float(t.x << 16), __uint_as_float(t.x & 0xffff0000u), __uint_as_float(t.y << 16),
-                 __uint_as_float(t.y & 0xffff0000u)};
-}
+__device__ __forceinline__ f32x4 mx_ld4(const unsigned short* p) { return bf16_unpack4(*reinterpret_cast<const uint2*>(p)); }
 
 template <int NV, class IN>
 __global__ __launch_bounds__(256) void quant_rows_mx_kernel(long rows, int K, const IN* __restrict__ x, long ldx,

@@ -19,6 +19,7 @@
 #include "common.h"
 #include "nce_index.h"
 #include "rng.h"
+#include "row_kit.h"
 
 #include "../../include/vilbert_hip_pretrain.h"
 
@@ -38,23 +39,6 @@ __device__ __forceinline__ float dot4(f32x4 a, f32x4 b, float acc) {
     acc = fmaf(a.y, b.y, acc);
     acc = fmaf(a.z, b.z, acc);
     return fmaf(a.w, b.w, acc);
-}
-
-// every thread gets the result; `scratch` holds one float per wave
-template <bool MAX>
-__device__ __forceinline__ float block_reduce(float v, float* scratch) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float o = __shfl_xor(v, off, 64);
-        v = MAX ? fmaxf(v, o) : v + o;
-    }
-    __syncthreads();                       // scratch may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < NCE_WAVES; ++w) r = MAX ? fmaxf(r, scratch[w]) : r + scratch[w];
-    return r;
 }
 
 __global__ __launch_bounds__(NCE_THREADS) void nce_negatives_kernel(long total, int n_neg, const int64_t* __restrict__ region,
@@ -131,10 +115,10 @@ __global__ __launch_bounds__(NCE_THREADS) void nce_fwd_kernel(long rows, int dim
         // ---- log-sum-exp over the C scores
         float m = -INFINITY;
         for (int c = tid; c < C; c += NCE_THREADS) m = fmaxf(m, s_w[c]);   // (fmaxf drops a NaN; the sum below keeps it)
-        m = block_reduce<true>(m, scratch);
+        m = block_reduce<true, NCE_THREADS>(m, scratch);
         float e = 0.f;
         for (int c = tid; c < C; c += NCE_THREADS) e += expf(s_w[c] - m);
-        e = block_reduce<false>(e, scratch);
+        e = block_reduce<false, NCE_THREADS>(e, scratch);
         const float lse = m + logf(e);
         block_loss += lse - s_w[0];                 // every thread holds the same value
         if (dsave == nullptr) continue;
@@ -178,7 +162,7 @@ __global__ __launch_bounds__(NCE_THREADS) void nce_finish_kernel(int n_partials,
     __shared__ float scratch[NCE_WAVES];
     float s = 0.f;
     for (int i = threadIdx.x; i < n_partials; i += NCE_THREADS) s += partials[i];
-    s = block_reduce<false>(s, scratch);
+    s = block_reduce<false, NCE_THREADS>(s, scratch);
     if (threadIdx.x == 0) loss[0] = s / count[0];
 }
 
@@ -198,11 +182,6 @@ __global__ __launch_bounds__(NCE_THREADS) void nce_bwd_kernel(long rows, int dim
     }
 }
 
-// a * b must stay inside int64 (the kernels index with it)
-inline bool extent_ok(int64_t a, int64_t b) { return a == 0 || b <= INT64_MAX / a; }
-
-inline bool vec_ok(const void* p, int64_t ld) { return vb_aligned16(p) && ld % 4 == 0; }
-
 }  // namespace
 
 extern "C" int vbp_nce_negatives(void* stream, int64_t rows, const int64_t* region_idx, int32_t batch, int32_t regions,
@@ -211,7 +190,7 @@ extern "C" int vbp_nce_negatives(void* stream, int64_t rows, const int64_t* regi
     const int64_t n_neg = (int64_t)n_across + (int64_t)n_inside;
     if (n_neg < 1 || (n_across > 0 && batch < 2) || (n_inside > 0 && regions < 2)) return VB_E_BADARG;
     if (!region_idx || !neg_idx) return VB_E_BADARG;
-    if (n_neg > INT32_MAX || !extent_ok(rows, 2 * n_neg) || !extent_ok((int64_t)batch * regions, 2 * n_neg)) return VB_E_RANGE;
+    if (n_neg > INT32_MAX || !vb_extent_ok(rows, 2 * n_neg) || !vb_extent_ok((int64_t)batch * regions, 2 * n_neg)) return VB_E_RANGE;
     if (rows == 0) return 0;
     const int64_t total = rows * n_neg;
     int64_t blocks = (total + NCE_THREADS - 1) / NCE_THREADS;
@@ -233,14 +212,14 @@ extern "C" int vbp_nce_fwd(void* stream, int64_t rows, int32_t dim, int32_t n_ne
     if (rows < 0 || dim < 1 || n_neg < 1 || table_rows < 1 || ldp < dim || ldt < dim || (dsave != nullptr && lds < dim))
         return VB_E_BADARG;
     if (!predict || !table || !pos_idx || !neg_idx || !count || !workspace || !loss) return VB_E_BADARG;
-    if (n_neg > NCE_MAX_NEG || !extent_ok(rows, ldp) || !extent_ok(rows, n_neg) || !extent_ok(table_rows, ldt) ||
-        (dsave != nullptr && !extent_ok(rows, lds)))
+    if (n_neg > NCE_MAX_NEG || !vb_extent_ok(rows, ldp) || !vb_extent_ok(rows, n_neg) || !vb_extent_ok(table_rows, ldt) ||
+        (dsave != nullptr && !vb_extent_ok(rows, lds)))
         return VB_E_RANGE;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const long blocks = rows < NCE_MAX_BLOCKS ? rows : NCE_MAX_BLOCKS;
     const size_t lds_bytes = (size_t)(1 + n_neg) * (sizeof(long) + sizeof(float));
-    const bool vec = vec_ok(predict, ldp) && vec_ok(table, ldt) && (dsave == nullptr || vec_ok(dsave, lds));
+    const bool vec = vb_row32_ok(predict, ldp) && vb_row32_ok(table, ldt) && (dsave == nullptr || vb_row32_ok(dsave, lds));
     if (vec)
         hipLaunchKernelGGL(nce_fwd_kernel<true>, dim3((unsigned)blocks), dim3(NCE_THREADS), lds_bytes, st, (long)rows, dim, n_neg,
                            predict, (long)ldp, table, (long)table_rows, (long)ldt, pos_idx, neg_idx, valid, count, workspace, loss,
@@ -261,7 +240,7 @@ extern "C" int vbp_nce_bwd(void* stream, int64_t rows, int32_t dim, const float*
                            const float* grad_loss, const float* count, float* dpredict, int64_t ldd) {
     if (rows < 0 || dim < 1 || lds < dim || ldd < dim) return VB_E_BADARG;
     if (!dsave || !grad_loss || !count || !dpredict) return VB_E_BADARG;
-    if (!extent_ok(rows, lds) || !extent_ok(rows, ldd)) return VB_E_RANGE;
+    if (!vb_extent_ok(rows, lds) || !vb_extent_ok(rows, ldd)) return VB_E_RANGE;
     if (rows == 0) return 0;
     const long blocks = rows < NCE_BWD_MAX_BLOCKS ? rows : NCE_BWD_MAX_BLOCKS;
     hipLaunchKernelGGL(nce_bwd_kernel, dim3((unsigned)blocks), dim3(NCE_THREADS), 0, (hipStream_t)stream, (long)rows, dim, dsave,

@@ -1,13 +1,15 @@
 // Row kernels of an output + feed-forward block that runs on a SUBSET of its rows (vb_ffn_block.row_map; layers.hip):
-//   gather        out[r] = src[map[r]]                                    (padding rows, map[r] = -1: zeros)
+//   move          out[r] = src[map[r]], 16-byte chunks of any element type  (padding rows, map[r] = -1: zeros); it serves
+//                 gather and scatter here and the bf16 head rows of heads16.hip
 //   drop + add    out[r] = dropout(lin[r]) + res[map[r] or r]             (the dropout / residual epilogue of the GEMMs, with
 //                                                                          the mask of the FULL tensor: keep(seed, map[r] N + col);
 //                                                                          without res: the dropped twin of a compact gradient)
 //   invert        inv[R] = the r with map[r] == R, or -1
 //   scatter       full[R] = compact[inv[R]]                               (rows no compact row stands for: zeros)
-// fp32, 16-byte accesses (cols % 4 == 0). The GEMM and LayerNorm kernels themselves know nothing of the map.
+// fp32 (the mover apart), 16-byte accesses (cols % 4 == 0). The GEMM and LayerNorm kernels themselves know nothing of the map.
 #include "common.h"
 #include "rng.h"
+#include "row_kit.h"
 #include "row_map.h"
 
 namespace {
@@ -17,14 +19,17 @@ __device__ __forceinline__ long source_row(const int32_t* __restrict__ map, long
     return s >= 0 && s < src_rows ? s : -1;        // (anything outside the full tensor is a padding row)
 }
 
-__global__ __launch_bounds__(256) void gather_rows_kernel(long M, int cols4, const f32x4* __restrict__ src,
-                                                          const int32_t* __restrict__ map, long src_rows,
-                                                          f32x4* __restrict__ out) {
-    const long n = M * cols4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const long r = i / cols4, c = i - r * cols4;
+// out[r] = src[map[r]] in 16-byte chunks, zeros for an entry outside the source; row strides in 16-byte units. The one mover
+// of the fp32 block rows (dense) and of the bf16 head rows (strided), gather and scatter alike: a scatter is the gather through
+// the inverse map.
+__global__ __launch_bounds__(256) void move_rows_kernel(long rows, int chunks, const v4i* __restrict__ src, long lds,
+                                                        long src_rows, const int32_t* __restrict__ map,
+                                                        v4i* __restrict__ out, long ldo) {
+    const long n = rows * chunks;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long r = i / chunks, c = i - r * chunks;
         const long s = source_row(map, r, src_rows);
-        out[i] = s >= 0 ? src[s * cols4 + c] : f32x4{0.f, 0.f, 0.f, 0.f};
+        out[r * ldo + c] = s >= 0 ? src[s * lds + c] : v4i{0, 0, 0, 0};
     }
 }
 
@@ -69,38 +74,27 @@ __global__ __launch_bounds__(256) void invert_map_kernel(long src_rows, int M, c
     if (lane == 0) inv[R] = found;
 }
 
-// full[R] = compact[inv[R]], zeros where no compact row stands for R
-__global__ __launch_bounds__(256) void scatter_rows_kernel(long src_rows, int cols4, const f32x4* __restrict__ compact,
-                                                           const int32_t* __restrict__ inv, f32x4* __restrict__ full) {
-    const long n = src_rows * cols4;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const long R = i / cols4, c = i - R * cols4;
-        const long r = inv[R];
-        full[i] = r >= 0 ? compact[r * cols4 + c] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-inline unsigned grid_for(long work_items) {
-    long blocks = (work_items + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    return (unsigned)blocks;
-}
+constexpr long ROW_MAX_BLOCKS = 2048;
 
 }  // namespace
 
 namespace vbrows {
 
-int gather(hipStream_t st, long M, int cols, const float* src, const int32_t* map, long src_rows, float* out) {
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(grid_for(M * (cols / 4))), dim3(256), 0, st, M, cols / 4,
-                       reinterpret_cast<const f32x4*>(src), map, src_rows, reinterpret_cast<f32x4*>(out));
+int move_rows(hipStream_t st, long rows, int chunks, const void* src, long lds, long src_rows, const int32_t* map, void* out,
+              long ldo, long max_blocks) {
+    hipLaunchKernelGGL(move_rows_kernel, dim3(vb_grid_for(rows * chunks, 256, max_blocks)), dim3(256), 0, st, rows, chunks,
+                       static_cast<const v4i*>(src), lds, src_rows, map, static_cast<v4i*>(out), ldo);
     VB_LAUNCH_CHECK();
     return 0;
 }
 
+int gather(hipStream_t st, long M, int cols, const float* src, const int32_t* map, long src_rows, float* out) {
+    return move_rows(st, M, cols / 4, src, cols / 4, src_rows, map, out, cols / 4, ROW_MAX_BLOCKS);
+}
+
 int drop_add(hipStream_t st, long M, int cols, const float* lin, const float* res, bool res_mapped, const int32_t* map,
              long src_rows, float* out, float p, uint64_t seed) {
-    hipLaunchKernelGGL(row_drop_add_kernel, dim3(grid_for(M * (cols / 4))), dim3(256), 0, st, M, cols / 4,
+    hipLaunchKernelGGL(row_drop_add_kernel, dim3(vb_grid_for(M * (cols / 4), 256, ROW_MAX_BLOCKS)), dim3(256), 0, st, M, cols / 4,
                        reinterpret_cast<const f32x4*>(lin), reinterpret_cast<const f32x4*>(res), res_mapped ? 1 : 0, map, src_rows,
                        reinterpret_cast<f32x4*>(out), p, 1.0f / (1.0f - p), seed, p > 0.f ? vb_seed_epoch() : nullptr);
     VB_LAUNCH_CHECK();
@@ -113,11 +107,8 @@ int invert(hipStream_t st, long src_rows, long M, const int32_t* map, int32_t* i
     return 0;
 }
 
-int scatter(hipStream_t st, long src_rows, int cols, const float* compact, const int32_t* inv, float* full) {
-    hipLaunchKernelGGL(scatter_rows_kernel, dim3(grid_for(src_rows * (cols / 4))), dim3(256), 0, st, src_rows, cols / 4,
-                       reinterpret_cast<const f32x4*>(compact), inv, reinterpret_cast<f32x4*>(full));
-    VB_LAUNCH_CHECK();
-    return 0;
+int scatter(hipStream_t st, long src_rows, int cols, const float* compact, long M, const int32_t* inv, float* full) {
+    return move_rows(st, src_rows, cols / 4, compact, cols / 4, M, inv, full, cols / 4, ROW_MAX_BLOCKS);
 }
 
 }  // namespace vbrows

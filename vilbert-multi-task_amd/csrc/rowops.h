@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "mx8.h"
+#include "row_kit.h"
 
 namespace vbrow {
 
@@ -46,10 +47,7 @@ struct RowBF16 {
     static constexpr unsigned ALIGN = 8;
     static constexpr bool PREFETCH = true;   // layernorm_bwd_kernel: request the next row before this row's reductions
     static __device__ __forceinline__ packed zero() { return uint2{0u, 0u}; }
-    static __device__ __forceinline__ f32x4 unpack(const packed w) {
-        return f32x4{__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xffff0000u), __uint_as_float(w.y << 16),
-                     __uint_as_float(w.y & 0xffff0000u)};
-    }
+    static __device__ __forceinline__ f32x4 unpack(const packed w) { return bf16_unpack4(w); }
     static __device__ __forceinline__ void store(elem* p, const f32x4 v) {
         *reinterpret_cast<uint2*>(p) = uint2{vb_bf16_pack(v[0], v[1]), vb_bf16_pack(v[2], v[3])};
     }

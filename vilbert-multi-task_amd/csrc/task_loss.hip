@@ -11,6 +11,7 @@
 // The forward is deterministic: no floating-point atomics - each block stores ONE partial sum to the caller's workspace
 // and a single block adds the partials in index order; a launch that needs one block only writes the loss itself.
 #include "common.h"
+#include "row_kit.h"
 
 #include "../../include/vilbert_hip_tasks.h"
 
@@ -21,18 +22,6 @@ constexpr int BCE_ROW_MIN_N = 256;          // rows at least this wide get a blo
 constexpr int BCE_FLAT_PER_BLOCK = 1024;    // elements a block of the flat mapping takes per grid stride (4 per thread)
 constexpr long BCE_MAX_PARTIALS = 1024;     // grid cap of the forward = workspace floats
 constexpr long BCE_BWD_MAX_BLOCKS = 65536;
-
-__device__ __forceinline__ float block_sum(float v, float* scratch) {
-    v = wave_sum(v);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();                       // scratch may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) scratch[wave] = v;
-    __syncthreads();
-    float r = scratch[0];
-#pragma unroll
-    for (int w = 1; w < TL_THREADS / 64; ++w) r += scratch[w];
-    return r;
-}
 
 // max(x, 0) - x t + log(1 + exp(-|x|)): exp never sees a positive argument, so nothing overflows at any x
 __device__ __forceinline__ float bce_term(float x, float t) {
@@ -71,7 +60,7 @@ __global__ __launch_bounds__(TL_THREADS) void bce_fwd_flat_kernel(long total, in
         }
         s += bce_term(logits[ox], target[ot]);
     }
-    s = block_sum(s, scratch);
+    s = block_reduce<false, TL_THREADS>(s, scratch);
     bce_store_partial(s, inv_count, partials, loss);
 }
 
@@ -86,18 +75,18 @@ __global__ __launch_bounds__(TL_THREADS) void bce_fwd_rows_kernel(long rows, int
         const float* t = target + r * ldt;
         for (int j = threadIdx.x; j < n; j += TL_THREADS) s += bce_term(x[j], t[j]);
     }
-    s = block_sum(s, scratch);
+    s = block_reduce<false, TL_THREADS>(s, scratch);
     bce_store_partial(s, inv_count, partials, loss);
 }
 
 // loss = inv_count * (partials[0] + partials[1] + ...): thread k adds partials k, k + 256, ... in that order, then the fixed
-// tree of block_sum - the same association on every run
+// tree of block_reduce - the same association on every run
 __global__ __launch_bounds__(TL_THREADS) void bce_finish_kernel(int n_partials, const float* __restrict__ partials,
                                                                 float inv_count, float* __restrict__ loss) {
     __shared__ float scratch[TL_THREADS / 64];
     float s = 0.f;
     for (int i = threadIdx.x; i < n_partials; i += TL_THREADS) s += partials[i];
-    s = block_sum(s, scratch);
+    s = block_reduce<false, TL_THREADS>(s, scratch);
     if (threadIdx.x == 0) loss[0] = s * inv_count;
 }
 
@@ -187,9 +176,6 @@ __global__ __launch_bounds__(TL_THREADS) void argmax_pick_kernel(long rows, int 
     }
 }
 
-// rows * ld must stay inside int64 (the kernels index with it)
-inline bool extent_ok(int64_t rows, int64_t ld) { return rows == 0 || ld <= INT64_MAX / rows; }
-
 inline long bce_fwd_blocks(int64_t rows, int32_t n) {
     if (n >= BCE_ROW_MIN_N) return rows < BCE_MAX_PARTIALS ? rows : BCE_MAX_PARTIALS;
     const int64_t b = (rows * n + BCE_FLAT_PER_BLOCK - 1) / BCE_FLAT_PER_BLOCK;
@@ -199,7 +185,7 @@ inline long bce_fwd_blocks(int64_t rows, int32_t n) {
 }  // namespace
 
 extern "C" int64_t vbt_bce_workspace(int64_t rows, int32_t n) {
-    if (rows <= 0 || n <= 0 || !extent_ok(rows, n)) return 0;
+    if (rows <= 0 || n <= 0 || !vb_extent_ok(rows, n)) return 0;
     return bce_fwd_blocks(rows, n);
 }
 
@@ -207,7 +193,7 @@ extern "C" int vbt_bce_fwd(void* stream, int64_t rows, int32_t n, const float* l
                            int64_t ldt, float* workspace, float* loss) {
     if (rows < 0 || n <= 0 || ld < n || ldt < n) return VB_E_BADARG;
     if (!logits || !target || !workspace || !loss) return VB_E_BADARG;
-    if (!extent_ok(rows, ld) || !extent_ok(rows, ldt)) return VB_E_RANGE;
+    if (!vb_extent_ok(rows, ld) || !vb_extent_ok(rows, ldt)) return VB_E_RANGE;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const long blocks = bce_fwd_blocks(rows, n);
@@ -230,7 +216,7 @@ extern "C" int vbt_bce_bwd(void* stream, int64_t rows, int32_t n, const float* l
                            int64_t ldt, const float* grad_loss, float* dlogits, int64_t ldd) {
     if (rows < 0 || n <= 0 || ld < n || ldt < n || ldd < n) return VB_E_BADARG;
     if (!logits || !target || !grad_loss || !dlogits) return VB_E_BADARG;
-    if (!extent_ok(rows, ld) || !extent_ok(rows, ldt) || !extent_ok(rows, ldd)) return VB_E_RANGE;
+    if (!vb_extent_ok(rows, ld) || !vb_extent_ok(rows, ldt) || !vb_extent_ok(rows, ldd)) return VB_E_RANGE;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const float inv_count = (float)(1.0 / ((double)rows * (double)n));
@@ -253,7 +239,7 @@ extern "C" int vbt_argmax_pick(void* stream, int64_t rows, int32_t n, const floa
                                int64_t ldl, int64_t* idx, float* picked, float* dense, int64_t ldo) {
     if (rows < 0 || n <= 0 || ld < n || ldl < n || (dense != nullptr && ldo < n)) return VB_E_BADARG;
     if (!logits || !labels || !idx || !picked) return VB_E_BADARG;
-    if (!extent_ok(rows, ld) || !extent_ok(rows, ldl) || (dense != nullptr && !extent_ok(rows, ldo))) return VB_E_RANGE;
+    if (!vb_extent_ok(rows, ld) || !vb_extent_ok(rows, ldl) || (dense != nullptr && !vb_extent_ok(rows, ldo))) return VB_E_RANGE;
     if (rows > (int64_t)INT32_MAX) return VB_E_RANGE;          // one block per row in the wide mapping: the grid's x extent
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;

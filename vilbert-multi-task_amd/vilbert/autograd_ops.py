@@ -291,16 +291,12 @@ class RaggedLinearFn(Function):
             G, GT, part = tag       # part: fp32 column sums of the unrounded loss gradient per 64 rows (cross entropy), or None
         else:
             dy2 = dy.reshape(rows, n)
-            if dy2.stride(1) != 1 or dy2.stride(0) % 4 != 0 or dy2.data_ptr() % 16 != 0:
-                dy2 = dy2.contiguous() if n % 4 == 0 else torch.nn.functional.pad(dy2, (0, 4 - n % 4))[:, :n]
             GT = None
             if ctx.bias_grad_f32 and bias is not None and ctx.needs_input_grad[2]:
                 # with the fp32 column sums of the gradient from the same pass: the bias gradient is not summed from rounded values
-                G, part = ops16.cast_rows_colsum(dy2)
+                G, part = ops16.cast_rows_colsum(ops16.rows_addressable(dy2))
             else:
-                G = torch.empty(rows, n_pad, dtype=BF16, device=dy.device)
-                N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), rows, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
-                                                      G.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
+                G = ops16.cast_rows_padded(dy2)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = ops16.linear_ragged_bwd_input(G, GT, weight, bias, rows).view(x.shape)

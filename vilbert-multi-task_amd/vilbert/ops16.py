@@ -262,12 +262,8 @@ def linear_bwd_weight_ragged(dy, x, want_bias, dw_out=None, db_out=None):
     M = x2.shape[0]
     if dy2.shape[0] != M:
         raise RuntimeError("linear_bwd_weight: row count mismatch")
-    if dy2.stride(1) != 1 or dy2.stride(0) % 4 != 0:
-        dy2 = dy2.contiguous() if n % 4 == 0 else torch.nn.functional.pad(dy2, (0, 4 - n % 4))[:, :n]
-    n_pad = (n + 255) // 256 * 256
-    dy16 = torch.empty(M, n_pad, dtype=BF16, device=dy.device)
-    N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), M, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
-                                          dy16.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
+    dy16 = cast_rows_padded(dy2)
+    n_pad = dy16.shape[1]
     x16 = cast_bf16(x2)
     dws, dbs = ops.wgrad_targets(1, n, K, want_bias, dw_out, db_out, dy.device)
     a = N.WgradBf16Args()
@@ -401,6 +397,27 @@ def colsum_parts(part, n, out=None):
     N.check(N.lib().vbh_colsum_parts(N.stream_ptr(), part.shape[0], n, N.dev_f32(part, "column-sum partials"), part.stride(0),
                                      N.dev_f32(out, "bias gradient")), "vbh_colsum_parts")
     return out
+
+
+def rows_addressable(dy2):
+    """The fp32 [rows, n] tensor as the 16-byte-row addressable view the row casts take (unit column stride, row stride % 4 == 0,
+    16-byte aligned); copies only if it has to."""
+    n = dy2.shape[1]
+    if dy2.stride(1) != 1 or dy2.stride(0) % 4 != 0 or dy2.data_ptr() % 16 != 0:
+        dy2 = dy2.contiguous() if n % 4 == 0 else torch.nn.functional.pad(dy2, (0, 4 - n % 4))[:, :n]
+    return dy2
+
+
+def cast_rows_padded(dy2):
+    """fp32 [rows, n] (any strides) -> bf16 [rows, padded(n)], pad columns zero: the padded operand of a ragged linear's
+    weight-gradient and input-gradient GEMMs."""
+    dy2 = rows_addressable(dy2)
+    rows, n = dy2.shape
+    n_pad = padded(n)
+    G = torch.empty(rows, n_pad, dtype=BF16, device=dy2.device)
+    N.check(N.lib().vb_cast_rows_f32_bf16(N.stream_ptr(), rows, n, N.dev_f32(dy2, "linear grad_output"), dy2.stride(0),
+                                          G.data_ptr(), n_pad), "vb_cast_rows_f32_bf16")
+    return G
 
 
 def cast_rows_colsum(dy):

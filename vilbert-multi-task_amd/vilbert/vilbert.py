@@ -1073,6 +1073,20 @@ class BertModel(BertPreTrainedModel):
         return encoded_layers_t, encoded_layers_v, pooled_output_t, pooled_output_v, all_attention_mask
 
 
+def _bf16_head_widths_ok(config, decoder_rows):
+    """Every pooler / prediction-head width passes the shape rules of the bf16 kernels (ops16.eligible: K % 128, widths % 256; the
+    bf16 LayerNorm: <= 1024 columns; the decoders - decoder_rows, v_target_size: any width through the zero-padded shadow) and
+    VB_BF16_HEADS is not 0. Shared by the pre-training and the fine-tuning wrapper."""
+    from . import ops16
+    H, Hv, Hb = config.hidden_size, config.v_hidden_size, config.bi_hidden_size
+
+    def out_ok(K, n):
+        return ops16.eligible(K, n) or ops16.ragged_ok(K, n)
+    return (ops16.heads_enabled() and ops16.eligible(H, Hb, act="relu") and ops16.eligible(Hv, Hb, act="relu")
+            and ops16.eligible(H, H) and ops16.eligible(Hv, Hv) and H <= 1024 and Hv <= 1024
+            and out_ok(H, decoder_rows) and out_ok(Hv, config.v_target_size))
+
+
 class BertForMultiModalPreTraining(BertPreTrainedModel):
     """Masked-LM + masked-region + alignment pre-training wrapper, reference vilbert.py:1435-1597."""
 
@@ -1180,15 +1194,7 @@ class BertForMultiModalPreTraining(BertPreTrainedModel):
     def _bf16_heads_ok(self):
         """Every pooler / head width passes the shape rules of the bf16 kernels (ops16.eligible: K % 128, widths % 256; the bf16
         LayerNorm: <= 1024 columns; the decoders: any width through the zero-padded shadow) and VB_BF16_HEADS is not 0."""
-        from . import ops16
-        c = self.config
-        H, Hv, Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
-
-        def out_ok(K, n):
-            return ops16.eligible(K, n) or ops16.ragged_ok(K, n)
-        return (ops16.heads_enabled() and ops16.eligible(H, Hb, act="relu") and ops16.eligible(Hv, Hb, act="relu")
-                and ops16.eligible(H, H) and ops16.eligible(Hv, Hv) and H <= 1024 and Hv <= 1024
-                and out_ok(H, self.cls.predictions.decoder.weight.size(0)) and out_ok(Hv, c.v_target_size))
+        return _bf16_head_widths_ok(self.config, self.cls.predictions.decoder.weight.size(0))
 
     def _losses_on_the_bf16_stream(self, sequence_output_t, sequence_output_v, masked_lm_labels, image_label, image_target,
                                    next_sentence_label):
@@ -1497,17 +1503,11 @@ class VILBertForVLTasks(BertPreTrainedModel):
         skinny-output kernels, and VB_BF16_HEADS is not 0."""
         from . import ops16
         c = self.config
-        H, Hv, Hb = c.hidden_size, c.v_hidden_size, c.bi_hidden_size
         pred, img = self.cls.predictions, self.cls.imagePredictions
-
-        def out_ok(K, n):
-            return ops16.eligible(K, n) or ops16.ragged_ok(K, n)
-        return (ops16.heads_enabled() and ops16.eligible(H, Hb, act="relu") and ops16.eligible(Hv, Hb, act="relu")
-                and ops16.eligible(H, H) and ops16.eligible(Hv, Hv) and H <= 1024 and Hv <= 1024
+        return (_bf16_head_widths_ok(c, pred.decoder.weight.size(0))
                 and pred.transform.transform_act_fn == "gelu" and img.transform.transform_act_fn == "gelu"
-                and out_ok(H, pred.decoder.weight.size(0)) and out_ok(Hv, c.v_target_size)
-                and ops16.skinny_ok(H, self.linguisic_logit.weight.size(0))
-                and ops16.skinny_ok(Hv, self.vision_logit.weight.size(0)))
+                and ops16.skinny_ok(c.hidden_size, self.linguisic_logit.weight.size(0))
+                and ops16.skinny_ok(c.v_hidden_size, self.vision_logit.weight.size(0)))
 
     def forward(self, input_txt, input_imgs, image_loc, token_type_ids=None, attention_mask=None,
                 image_attention_mask=None, co_attention_mask=None, task_ids=None,
