@@ -127,6 +127,8 @@ int vb_set_gemm_v4(int mode);
  * activation (gelu: 0.5 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi); relu: x > 0) - saved by the
  * training forward so that the backward of `act` is ONE multiply in the epilogue of vb_linear_bwd_input
  * (its `mul` argument) instead of a separate erf / exp pass over [M, N].
+ * preact and act_grad are alternatives: a launch that asks for both returns VB_E_BADARG, in every GEMM mode (no kernel
+ * stores both; the training forward saves one or the other). Pinned by tests/test_gemm_planes_gpu.py.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t M, K;
@@ -153,6 +155,10 @@ int vb_linear_fwd(void* stream, const vb_linear_args* a);
  * vilbert.py:516 and its twins), added in the epilogue instead of by a separate pass.
  * mul (ldm, may be NULL): [M, K] elementwise multiplier of the result, dX = (dY . stack(W) + residual) * mul -
  * the act_grad saved by the forward of the Linear that PRODUCED this layer's input (gelu backward fused here).
+ * mul together with accumulate != 0 returns VB_E_BADARG, in every GEMM mode (the multiplier applies to the whole result,
+ * which a launch that adds into dX does not hold; no caller accumulates through an activation). With nseg > 1 segments
+ * whose size is not a multiple of 16 the call runs one launch per segment, and residual or mul return VB_E_SEGMENT.
+ * An error return leaves dX untouched. Pinned by tests/test_gemm_planes_gpu.py.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t M, K;
@@ -173,7 +179,7 @@ int vb_linear_bwd_input(void* stream, const vb_linear_bwd_input_args* a);
  * Gradient of nn.Linear w.r.t. weight and bias of the nseg stacked segments (dY is [M, nseg*seg_n]
  * with row stride ldy). The contraction over the M rows is split over workgroups and combined with
  * fp32 atomics; the bias gradient is fused into the same launch. dbias[s] may be NULL.
- * accumulate == 0 zero-fills dW / dbias first.
+ * accumulate == 0 zero-fills dW / dbias first. An error return leaves every target untouched.
  * ------------------------------------------------------------------------------------------ */
 typedef struct {
     int32_t M, K;

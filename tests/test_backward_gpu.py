@@ -177,7 +177,9 @@ def test_bi_attention_node_with_one_direction_in_the_loss(dtype):
         assert l2 <= 1.5e-2 and mx <= 2.0 ** -6, "relative L2 %.3e, max error %.3e of the range" % (l2, mx)
 
 
-def _grad_parity(cfg, kind, batch, n_tok, n_reg, seed=5):
+def _grad_parity(cfg, kind, batch, n_tok, n_reg, seed=5, slack=1.0):
+    """slack: factor on the bounds ASSERTED here (1 = the criterion itself; an arithmetic with a bound of its own measured
+    against this criterion passes its bound); the returned ratio is always relative to the criterion."""
     from vilbert.vilbert import BertConfig, BertForMultiModalPreTraining, VILBertForVLTasks
     sd = synth.make_state_dict(cfg, kind, seed=seed)
     x = synth.make_inputs(cfg, batch, n_tok, n_reg, seed=seed, with_labels=(kind == "pretraining"),
@@ -207,7 +209,7 @@ def _grad_parity(cfg, kind, batch, n_tok, n_reg, seed=5):
         w8 = [1.0, 0.7, 1.3, 0.9, 1.1, 0.01, None, 0.002, 1.0]
         loss_g = sum((w * o).sum() for w, o in zip(w8, got) if w is not None) + (got[6] * m.to(DEV)).sum()
         loss_w = sum((w * o).sum() for w, o in zip(w8, want) if w is not None) + (want[6] * m).sum()
-    helpers.assert_close(loss_g, loss_w, "loss", atol=1e-4 * max(1.0, abs(loss_w.item())))
+    helpers.assert_close(loss_g, loss_w, "loss", atol=slack * 1e-4 * max(1.0, abs(loss_w.item())), rtol=slack * helpers.RTOL)
     loss_g.backward()
     loss_w.backward()
     # Criterion per parameter tensor: |got - ref| <= 2e-4 * max|ref| + 2e-7 * (largest gradient entry in
@@ -225,8 +227,8 @@ def _grad_parity(cfg, kind, batch, n_tok, n_reg, seed=5):
         scale = ref.abs().max().item()
         err = (p.grad.cpu().double() - ref.double()).abs().max().item()
         bound = 2e-4 * scale + 2e-7 * gmax
-        assert err <= bound, "%s: grad err %.3e > bound %.3e (max|ref| %.3e, model max %.3e)" % (
-            name, err, bound, scale, gmax)
+        assert err <= slack * bound, "%s: grad err %.3e > bound %.3e (max|ref| %.3e, model max %.3e)" % (
+            name, err, slack * bound, scale, gmax)
         worst = max(worst, err / bound)
     return worst
 

@@ -514,7 +514,7 @@ int launch_gemm(hipStream_t st, GemmP p, bool vec, int splits, int legacy_splits
         p.ktiles_per_split = (kt_total + splits - 1) / splits;
         splits = (kt_total + p.ktiles_per_split - 1) / p.ktiles_per_split;
         if (det_on() && splits > 1) {
-            p.det_cs_parts = planes != 0 ? 2 : 1;
+            p.det_cs_parts = 1;   // one bias-gradient partial per (split, row) on every kernel
             det_legacy = p.N % 4 == 0 && det_prepare(st, p, splits);
             if (!det_legacy) { splits = 1; p.ktiles_per_split = kt_total; }
         }
@@ -599,7 +599,9 @@ extern "C" int vb_linear_bwd_input(void* stream, const vb_linear_bwd_input_args*
     // a K tile of the contraction (over out-features) must not straddle two weight segments; otherwise
     // run one launch per segment, accumulating.
     const bool fused = a->nseg == 1 || (a->seg_n % BK) == 0;
-    if (!fused && a->residual != nullptr) return VB_E_SEGMENT;
+    if (!fused && (a->residual != nullptr || a->mul != nullptr)) return VB_E_SEGMENT;
+    for (int s = 0; s < a->nseg; ++s)       // (before the first launch: an error return leaves dX untouched)
+        if (a->W[s] == nullptr) return VB_E_SEGMENT;
     const int launches = fused ? 1 : a->nseg;
     for (int l = 0; l < launches; ++l) {
         GemmP p{};
@@ -675,8 +677,9 @@ extern "C" int vb_linear_bwd_weight(void* stream, const vb_linear_bwd_weight_arg
     if (a->M <= 0 || a->K <= 0 || a->seg_n <= 0) return VB_E_BADARG;
     if (a->nseg < 1 || a->nseg > VB_MAX_SEGMENTS) return VB_E_SEGMENT;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (int s = 0; s < a->nseg; ++s) {
+    for (int s = 0; s < a->nseg; ++s)       // (before the first zero fill: an error return leaves every target untouched)
         if (a->dW[s] == nullptr) return VB_E_SEGMENT;
+    for (int s = 0; s < a->nseg; ++s) {
         if (!a->accumulate) {
             if (int e = zero_rows(st, a->dW[s], a->ldw, a->seg_n, a->K)) return e;
             if (a->dbias[s] != nullptr)

@@ -50,7 +50,7 @@ struct GemmP {
     // plain [M, N] matrix (and its bias-gradient partial to det_cs + s * M) instead of adding into C with atomics; a
     // second kernel sums the partials in split order (splitk_reduce_kernel)
     float* det_ws; float* det_cs; long det_stride;
-    int det_cs_parts;          // bias-gradient partials per (split, row): 1, or 2 for the bf16-plane kernels (two threads per row)
+    int det_cs_parts;          // bias-gradient partials per (split, row): 1 (the plane kernels add their two k halves first)
 };
 // passed BY VALUE to every GEMM kernel: neither size nor field order may change
 static_assert(sizeof(GemmP) == 360, "GemmP is a kernel argument: keep its layout");

@@ -300,7 +300,17 @@ __device__ __forceinline__ void gemm_tile_planes(const GemmP& p, char* __restric
         else kstep(kt, ra2, rb2, ra, rb, ld, stq);
     }
 
-    tile_epilogue<TM, TN, A_KC, B_KC>(p, acc, m0, n0, want_colsum, csum, ua_row, ua_half);   // two threads hold a row's sum
+    // Bias gradient: two threads (the two k halves) hold a row's sum. They are added HERE, in a fixed order, and one of them
+    // hands the row to the epilogue: two atomic adds per row into a target that already holds a contribution would
+    // depend on their order in the last bit (the unsplit launch has no ordered reduce behind it). The stage buffers are
+    // free after the barrier that ends the last K step. (n0 and colsum are block-uniform: every thread meets the barrier.)
+    if (!A_KC && n0 == 0 && p.colsum[0] != nullptr) {
+        float* __restrict__ xs = reinterpret_cast<float*>(smem);
+        if (ua_on && ua_half == 1) xs[ua_row] = csum;
+        __syncthreads();
+        if (ua_on && ua_half == 0) csum += xs[ua_row];
+    }
+    tile_epilogue<TM, TN, A_KC, B_KC>(p, acc, m0, n0, want_colsum && ua_half == 0, csum, ua_row);
 }
 
 template <bool A_KC, bool B_KC, bool VEC, int NPL>
