@@ -449,6 +449,12 @@ int vb_additive_mask(void* stream, int64_t n, const void* mask, int32_t mask_is_
  * f(seed, ((b * heads + h) * n_q + q) * n_k + key) with THIS launch's n_k (a key chunk of a longer sequence, below,
  * counts its own keys from 0: the caller gives every chunk its own seed).
  * head_dim in {32, 64, 128}; n_k <= VB_MAX_KEYS.
+ * Alignment (VB_E_ALIGN otherwise, checked before anything is launched): the tensors the kernels READ with 16-byte loads -
+ * Q, K, V and the backward's dO - need a 16-byte aligned pointer and a row stride (ldq, ldk, ldv, lddo: floats) % 4 == 0.
+ * The OUTPUTS O, dQ, dK, dV are written one float at a time: any float pointer, any row stride >= heads * head_dim; the
+ * strides are independent of each other (ldk != ldv, lddq != lddk != lddv are fine). Output strides only choose the kernel:
+ * with at most 48 queries and keys the one-launch backward takes lddq, lddk, lddv all % 4 == 0, any other strides run the
+ * two-launch backward (the same formulas). probs, lse, dvec and mask_add are dense.
  *
  * vb_attention_bwd: given the same arguments (lse filled by the forward, probs ignored) and dO,
  * writes dQ / dK / dV (each element exactly once - they may be column slices of one fused gradient
@@ -458,7 +464,8 @@ int vb_additive_mask(void* stream, int64_t n, const void* mask, int32_t mask_is_
  * caller cuts the keys into chunks of <= VB_MAX_KEYS, passes `lse` = the log-sum-exp over ALL keys (the merge of the
  * chunk forwards) and calls the backward per chunk twice: dvec_mode = VB_DVEC_ACCUMULATE adds this chunk's share of
  * D = rowsum(P dP) to `dvec` (zeroed by the caller; nothing else is written), then dvec_mode = VB_DVEC_GIVEN computes
- * this chunk's dK / dV and its share of dQ from the complete D (the caller sums the dQ shares).
+ * this chunk's dK / dV and its share of dQ from the complete D (the caller sums the dQ shares). The argument checks do not
+ * depend on dvec_mode: an ACCUMULATE call passes valid dQ / dK / dV too (NULL is VB_E_BADARG), it just leaves them alone.
  * ------------------------------------------------------------------------------------------ */
 #define VB_DVEC_COMPUTE 0
 #define VB_DVEC_ACCUMULATE 1
@@ -618,8 +625,9 @@ int vb_concap_finish_batch(void* stream, const vb_concap_batch* a);
  * ------------------------------------------------------------------------------------------ */
 /* Attention of the bf16 training path: exactly vb_attention_fwd / vb_attention_bwd (same kernels, csrc/attention.hip
  * compiled with -DVB_ATTN_BF16; same argument meaning, same limits) with Q, K, V, O and dO, dQ, dK, dV as bf16 bit patterns
- * (row strides in ELEMENTS % 4 == 0, pointers 8-byte aligned); mask_add, probs, lse and dvec stay fp32; the operands are
- * widened to fp32 on their way into registers / LDS, products on the exact-fp32 MFMA, fp32 softmax. */
+ * (row strides in ELEMENTS % 4 == 0, pointers 8-byte aligned - all eight of them, the outputs included, which are stored two
+ * columns per dword; anything else is VB_E_ALIGN before a kernel is launched); mask_add, probs, lse and dvec stay fp32; the
+ * operands are widened to fp32 on their way into registers / LDS, products on the exact-fp32 MFMA, fp32 softmax. */
 typedef struct {
     int32_t batch, heads, head_dim, n_q, n_k;
     int32_t q_batch, kv_batch;

@@ -989,6 +989,16 @@ typedef vb_attention_grads attn_grads_t;
 constexpr unsigned IO_ALIGN = 15u;
 #endif
 inline bool io_aligned(const void* q) { return (reinterpret_cast<uintptr_t>(q) & IO_ALIGN) == 0; }
+// O, dQ, dK, dV. bf16 build: store_cols writes two adjacent columns as one dword at an even element offset of the row, so the
+// header's rule for every bf16 tensor (row stride % 4 == 0, pointer 8-byte aligned) holds for the outputs too. fp32 build:
+// one scalar store per element - any row stride, any float pointer.
+inline bool out_aligned(const void* q, long ld) {
+#ifdef VB_ATTN_BF16
+    return ld % 4 == 0 && io_aligned(q);
+#else
+    return true;
+#endif
+}
 
 int fill_common(AttnP& p, const attn_args_t* a) {
     if (a == nullptr || a->Q == nullptr || a->K == nullptr || a->V == nullptr) return VB_E_BADARG;
@@ -1018,6 +1028,7 @@ extern "C" int VB_ATTN_FWD(void* stream, const attn_args_t* a) {
     AttnP p{};
     if (int e = fill_common(p, a)) return e;
     if (a->O == nullptr) return VB_E_BADARG;
+    if (!out_aligned(a->O, a->ldo)) return VB_E_ALIGN;
     p.O = a->O; p.ldo = a->ldo; p.probs = a->probs;
     p.total = (long)a->batch * a->heads * p.n_qt;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1037,6 +1048,7 @@ extern "C" int VB_ATTN_BWD(void* stream, const attn_args_t* a, const attn_grads_
         return VB_E_BADARG;
     if (a->q_batch != a->batch || a->kv_batch != a->batch) return VB_E_BADARG;  // no broadcast in training
     if (gr->lddo % 4 != 0 || !io_aligned(gr->dO)) return VB_E_ALIGN;
+    if (!out_aligned(gr->dQ, gr->lddq) || !out_aligned(gr->dK, gr->lddk) || !out_aligned(gr->dV, gr->lddv)) return VB_E_ALIGN;
     p.dO = gr->dO; p.lddo = gr->lddo;
     p.dQ = gr->dQ; p.lddq = gr->lddq; p.dK = gr->dK; p.lddk = gr->lddk; p.dV = gr->dV; p.lddv = gr->lddv;
     p.dvec = gr->dvec;
