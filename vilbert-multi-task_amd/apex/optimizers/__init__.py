@@ -17,10 +17,13 @@ owns the arena, whatever the order in which optimizer and DistributedDataParalle
 on the device and the update kernel multiplies it in as it loads the gradients; `.grad` is not rewritten (apex passes its
 scale to the kernel the same way). As in apex, a step whose gradients hold an inf / NaN is skipped - parameters and moments
 keep their bits - and `FP16_Optimizer.overflow` reports it.
+
+`FusedLAMB` stands next to `FusedAdam` as it does in apex: the optimizer for pre-training at a global batch of thousands of
+samples, on the native LAMB step (vilbert.optim.LAMB, csrc/lamb.hip), inside the same `FP16_Optimizer`.
 """
 import torch
 
-from vilbert.optim import AdamW
+from vilbert.optim import LAMB, AdamW
 
 
 class FusedAdam(AdamW):
@@ -50,6 +53,36 @@ class FusedAdam(AdamW):
 
     def step(self, closure=None, **_apex_kwargs):      # (apex passes grads / output_params / scale / grad_norms)
         return super(FusedAdam, self).step(closure)
+
+
+class FusedLAMB(LAMB):
+    """apex.optimizers.FusedLAMB's constructor on the native LAMB step (vilbert.optim.LAMB, csrc/lamb.hip): the optimizer
+    to select when pre-training at a global batch of thousands of samples. As FusedAdam above, a step whose gradients hold
+    an inf / NaN is skipped. Differences from apex, whose bits nothing here is pinned against (apex does not exist on ROCm
+    images): the step count - and with it the bias correction - is kept per tensor, not per group (a tensor that misses a
+    gradient falls behind, as in every optimizer of this package); the clip coefficient is the package's own,
+    min(1, max_grad_norm / (||g|| + 1e-6)) of ``torch.nn.utils.clip_grad_norm_``, where apex divides by
+    ||g|| / max_grad_norm when that exceeds 1; fp16 parameter lists and AMSGrad are not offered. ``set_grad_none`` is the default of
+    ``zero_grad()``'s ``set_to_none``."""
+
+    def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01,
+                 amsgrad=False, adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0,
+                 use_nvlamb=False):
+        if amsgrad:
+            raise RuntimeError("FusedLAMB does not support the AMSGrad variant.")
+        super(FusedLAMB, self).__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
+                                        bias_correction=bias_correction, grad_averaging=grad_averaging,
+                                        adam_w_mode=adam_w_mode, use_nvlamb=use_nvlamb, max_grad_norm=max_grad_norm,
+                                        skip_nonfinite=True)
+        self.set_grad_none = bool(set_grad_none)
+
+    _PICKLED = LAMB._PICKLED + ("set_grad_none",)
+
+    def zero_grad(self, set_to_none=None):
+        super(FusedLAMB, self).zero_grad(set_to_none=self.set_grad_none if set_to_none is None else set_to_none)
+
+    def step(self, closure=None, **_apex_kwargs):      # (apex passes grads / output_params / scale / grad_norms)
+        return super(FusedLAMB, self).step(closure)
 
 
 class FP16_Optimizer(torch.optim.Optimizer):

@@ -276,6 +276,16 @@ class RAdamScalars(ctypes.Structure):
     ]
 
 
+class LambScalars(ctypes.Structure):
+    """vbl_lamb_scalars (52 bytes; include/vilbert_hip_lamb.h)"""
+    _fields_ = [
+        ("lr", ctypes.c_float), ("weight_decay", ctypes.c_float), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float),
+        ("beta3", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("bc1", ctypes.c_float), ("bc2", ctypes.c_float),
+        ("eps", ctypes.c_float), ("adam_w_mode", ctypes.c_int32), ("apply_trust", ctypes.c_int32),
+        ("first_chunk", ctypes.c_int32), ("n_chunks", ctypes.c_int32),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -411,6 +421,13 @@ FINETUNE_SIGNATURES = {
     "vbf_cast_rows_colsum": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _I64, _P]),
 }
 
+# include/vilbert_hip_lamb.h (the LAMB step: per-tensor trust ratios on the multi-tensor launch tables; prefix vbl_), mirrored
+# one to one (checked by tests/test_lamb.py)
+LAMB_SIGNATURES = {
+    "vbl_lamb_workspace": (_I64, [_I32]),
+    "vbl_lamb_step": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _I32]),
+}
+
 _lib = None
 
 
@@ -425,7 +442,8 @@ def lib():
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
-                                  + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())):
+                                  + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
+                                  + list(LAMB_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

@@ -8,6 +8,9 @@ unchanged reference scripts pick it up.
 RAdam / PlainRAdam (the reference's own ``vilbert/optimization.py``, ``train_tasks.py --optim RAdam``) run on the same
 plumbing with a kernel of their own (``vbo_radam_step``); ``import vilbert.optimization`` hands them out under the
 reference's import path (vilbert/__init__.py: _OptimizationFinder).
+
+LAMB (layer-wise trust ratios, for pre-training at a large global batch) runs on the same plumbing as two launches with
+per-tensor norms (csrc/lamb.hip, ``vbl_lamb_step``); ``apex.optimizers.FusedLAMB`` is apex's constructor on top of it.
 """
 import ctypes
 import math
@@ -28,6 +31,10 @@ _TABLE_DTYPE = np.dtype([
 _RADAM_DTYPE = np.dtype([
     ("step_size", "<f4"), ("decay", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("one_minus_beta1", "<f4"),
     ("one_minus_beta2", "<f4"), ("eps", "<f4"), ("rectified", "<i4")])
+_LAMB_DTYPE = np.dtype([
+    ("lr", "<f4"), ("weight_decay", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("beta3", "<f4"), ("one_minus_beta2", "<f4"),
+    ("bc1", "<f4"), ("bc2", "<f4"), ("eps", "<f4"), ("adam_w_mode", "<i4"), ("apply_trust", "<i4"), ("first_chunk", "<i4"),
+    ("n_chunks", "<i4")])
 
 
 def _check_clip_args(max_grad_norm, grad_scale):
@@ -420,6 +427,133 @@ class RAdam(PlainRAdam):
 # native class here and vice versa (vilbert/utils.py does the same for the reference's logging classes). The finder in
 # vilbert/__init__.py makes `vilbert.optimization.RAdam` this very class.
 RAdam.__module__ = PlainRAdam.__module__ = "vilbert.optimization"
+
+
+class LAMB(_MultiTensorOptimizer):
+    """LAMB (You et al. 2020, "Large Batch Optimization for Deep Learning: Training BERT in 76 minutes"): Adam with one trust
+    ratio ||p|| / ||update|| per parameter tensor, the optimizer BERT pre-training uses at global batches of thousands of
+    samples. Two native launches after the optional norm pass (csrc/lamb.hip, include/vilbert_hip_lamb.h). Per tensor, in
+    fp32 on the device, with g the gradient times the base class's clip / scale coefficient:
+
+        L2 mode (adam_w_mode=False):  g += weight_decay * p
+        m = beta1 * m + beta3 * g             beta3 = 1 - beta1 with grad_averaging, else 1
+        v = beta2 * v + (1 - beta2) * g * g
+        u = (m / bc1) / (sqrt(v / bc2) + eps)  [+ weight_decay * p  with adam_w_mode]
+                                              bc = 1 - beta^t with bias_correction, else 1; t = the tensor's own 1-based step count
+        r = ||p|| / ||u||  if (use_nvlamb or weight_decay != 0) and ||p|| > 0 and ||u|| > 0, else 1
+        p = p - lr * r * u
+
+    ``lr``, ``betas``, ``eps``, ``weight_decay``, ``bias_correction`` and ``grad_averaging`` are per parameter group;
+    ``adam_w_mode`` and ``use_nvlamb`` hold for the whole optimizer. The scalars of a step are computed on the host in double
+    and rounded once to float. State layout (``step``, ``exp_avg``, ``exp_avg_sq``) as the other classes of this module.
+    ``max_grad_norm`` (default 1.0, as LAMB is usually run), ``grad_scale`` and ``skip_nonfinite`` are those of the base
+    class; a skipped step leaves parameters, moments and ``trust_ratios`` untouched. The norms are summed without atomics in a
+    fixed order: the same inputs give the same bits, wherever a tensor stands in the parameter list. Unlike the other classes
+    a pickled LAMB keeps its optimizer-wide settings."""
+
+    _NAME = "LAMB"
+    _SPARSE_MESSAGE = "LAMB does not support sparse gradients"
+    _EXTRA_DTYPE = _LAMB_DTYPE
+    _PICKLED = ("adam_w_mode", "use_nvlamb", "max_grad_norm", "grad_scale", "skip_nonfinite")
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, bias_correction=True,
+                 grad_averaging=True, adam_w_mode=True, use_nvlamb=False, max_grad_norm=1.0, grad_scale=1.0,
+                 skip_nonfinite=False):
+        if lr < 0.0:
+            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+        if not 0.0 <= eps:
+            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        self._init_native(max_grad_norm, grad_scale, skip_nonfinite)
+        self.adam_w_mode, self.use_nvlamb = bool(adam_w_mode), bool(use_nvlamb)
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bool(bias_correction),
+                        grad_averaging=bool(grad_averaging))
+        super(LAMB, self).__init__(params, defaults)
+        self._init_plan()
+
+    def __getstate__(self):
+        state = dict(super(LAMB, self).__getstate__())
+        state.update((k, getattr(self, k)) for k in self._PICKLED)
+        return state
+
+    def __setstate__(self, state):
+        super(LAMB, self).__setstate__(state)          # (the base class puts the clipping attributes back at ITS defaults)
+        for k in self._PICKLED:
+            if k in state:
+                setattr(self, k, state[k])
+
+    def _fill_hyper(self, plan, entries):
+        """(vectorised, as AdamW's; a tensor's chunks are consecutive in the chunk list, so its first chunk is the number of
+        chunks in front of it)"""
+        assert ctypes.sizeof(N.LambScalars) == _LAMB_DTYPE.itemsize
+        extra, n = plan["extra"], len(entries)
+        gi = self._group_index(plan, entries)
+        groups = self.param_groups
+        lr = np.array([g["lr"] for g in groups], dtype=np.float64)[gi]
+        b1 = np.array([g["betas"][0] for g in groups], dtype=np.float64)[gi]
+        b2 = np.array([g["betas"][1] for g in groups], dtype=np.float64)[gi]
+        eps = np.array([g["eps"] for g in groups], dtype=np.float64)[gi]
+        wd = np.array([g["weight_decay"] for g in groups], dtype=np.float64)[gi]
+        corr = np.array([bool(g["bias_correction"]) for g in groups])[gi]
+        avg = np.array([bool(g["grad_averaging"]) for g in groups])[gi]
+        steps = np.fromiter((st["step"] for _p, st, _g in entries), dtype=np.float64, count=n)
+        extra["lr"], extra["weight_decay"], extra["beta1"], extra["beta2"], extra["eps"] = lr, wd, b1, b2, eps
+        extra["beta3"] = np.where(avg, 1.0 - b1, 1.0)
+        extra["one_minus_beta2"] = 1.0 - b2
+        extra["bc1"] = np.where(corr, 1.0 - b1 ** steps, 1.0)
+        extra["bc2"] = np.where(corr, 1.0 - b2 ** steps, 1.0)
+        extra["adam_w_mode"] = int(self.adam_w_mode)
+        extra["apply_trust"] = (wd != 0.0) | self.use_nvlamb
+        if "lamb_index" not in plan:
+            counts = -(-plan["tab"]["numel"] // CHUNK_ELEMS)
+            plan["lamb_chunks"] = (np.cumsum(counts) - counts, counts)
+            plan["lamb_index"] = {id(p): i for i, (p, _st, _g) in enumerate(entries)}
+        extra["first_chunk"], extra["n_chunks"] = plan["lamb_chunks"]
+
+    def _lamb_buffers(self, plan):
+        """Fixed-address buffers of the two stages, both the plan's: the per-chunk partial sums of p^2 and u^2 and the
+        per-tensor trust ratios (1 until a step has run)."""
+        if "trust" not in plan:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(self._NAME + ": the first step of a plan allocates its trust-ratio buffers and must run "
+                                   "eagerly before a graph capture (GraphedTrainStep's warm-up does)")
+            device = plan["dev_tab"].device
+            plan["lamb_workspace"] = torch.empty(int(N.lib().vbl_lamb_workspace(plan["n_chunks"])), dtype=torch.float32,
+                                                 device=device)
+            plan["trust"] = torch.ones(len(plan["tab"]), dtype=torch.float32, device=device)
+        return plan["lamb_workspace"], plan["trust"]
+
+    def _launch(self, plan, state, skip):
+        workspace, trust = self._lamb_buffers(plan)
+        N.check(N.lib().vbl_lamb_step(N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), self._extra_ptr(plan),
+                                      plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
+                                      workspace.data_ptr(), trust.data_ptr(), None if state is None else state.data_ptr(),
+                                      skip), "vbl_lamb_step")
+
+    def _need_trust(self):
+        if self._plan is None or "trust" not in self._plan:
+            raise RuntimeError(self._NAME + ": no step has run yet - there are no trust ratios")
+        return self._plan
+
+    @property
+    def trust_ratios(self):
+        """The trust ratio r of every tensor the last step updated, in the order the step walked them (parameter groups in
+        order, parameters without a gradient left out): a DEVICE tensor the update kernel writes - reading the property does
+        not synchronise, and the same tensor shows the values of every later step with the same set of tensors (also of
+        graph replays). Clone it to keep the values."""
+        return self._need_trust()["trust"]
+
+    def trust_ratio(self, p):
+        """The 0-dim device view of `trust_ratios` for parameter `p`."""
+        plan = self._need_trust()
+        i = plan["lamb_index"].get(id(p))
+        if i is None:
+            raise KeyError(self._NAME + ": the last step did not update this tensor (no gradient, or not a parameter of this "
+                           "optimizer)")
+        return plan["trust"][i]
 
 
 class ConstantLRSchedule(LambdaLR):
