@@ -286,6 +286,19 @@ class LambScalars(ctypes.Structure):
     ]
 
 
+class MaskArgs(ctypes.Structure):
+    """vbi_mask_args (104 bytes; include/vilbert_hip_inputs.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("tokens", ctypes.c_int32), ("regions", ctypes.c_int32),
+        ("vocab_size", ctypes.c_int32), ("mask_token_id", ctypes.c_int32), ("p_select", ctypes.c_float),
+        ("seed", ctypes.c_uint64),
+        ("input_ids", ctypes.c_void_p), ("input_mask", ctypes.c_void_p), ("image_mask", ctypes.c_void_p),
+        ("overlaps", ctypes.c_void_p),
+        ("out_input_ids", ctypes.c_void_p), ("lm_label_ids", ctypes.c_void_p), ("image_label", ctypes.c_void_p),
+        ("masked_label", ctypes.c_void_p), ("zero_row", ctypes.c_void_p),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -428,6 +441,13 @@ LAMB_SIGNATURES = {
     "vbl_lamb_step": (ctypes.c_int, [_P, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _I32]),
 }
 
+# include/vilbert_hip_inputs.h (device-side MLM and region masking of a pre-training batch; prefix vbi_), mirrored one to one
+# (checked by tests/test_mask_batch.py)
+INPUT_SIGNATURES = {
+    "vbi_concap_mask_batch": (ctypes.c_int, [_P, ctypes.POINTER(MaskArgs)]),
+    "vbi_zero_rows": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _I64]),
+}
+
 _lib = None
 
 
@@ -443,7 +463,7 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
                                   + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
-                                  + list(LAMB_SIGNATURES.items())):
+                                  + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

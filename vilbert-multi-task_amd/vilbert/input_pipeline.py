@@ -11,6 +11,13 @@ the previous step computes (double buffered), and finished by one native pass (c
 unpacks after its own ``.cuda()`` calls and label edit:
     (input_ids, input_mask, segment_ids, lm_label_ids, is_next, image_feat, image_loc, image_target,
      image_label, image_mask)
+
+Dynamic masking (opt-in, ``DeviceBatchPipeline(..., masking=Masking(...))``): the source keeps UNMASKED samples
+(``RAW_UNMASKED_FIELDS``: the pairwise IoU of the boxes travels in the slot of ``masked_label``) and which tokens and
+regions a step predicts is drawn on the device by ``mask_batch`` (csrc/mask_batch.hip, ``vbi_concap_mask_batch`` +
+``vbi_zero_rows``) right before ``finish_batch``. The per-site rule and the probabilities are those of the reference's
+``random_word`` / ``random_region``; the draws come from the library's counter-based hash, NOT from Python's ``random``
+stream, so the masks of a run differ from the reference's while having the same distribution.
 """
 import ctypes
 import os
@@ -23,9 +30,127 @@ from . import _native as N
 # order of the raw tuple produced by the dataset workers (concept_cap_dataset.py:243-245)
 RAW_FIELDS = ("input_ids", "input_mask", "segment_ids", "lm_label_ids", "is_next", "image_feat", "image_loc",
               "image_target", "image_label", "image_mask", "masked_label")
+# the same tuple from a source that selects nothing (unmasked_preprocess): the [regions, regions] IoU matrix of the boxes
+# stands where masked_label stood, lm_label_ids / image_label are all -1 and are replaced by mask_batch
+RAW_UNMASKED_FIELDS = tuple("overlaps" if n == "masked_label" else n for n in RAW_FIELDS)
 _DTYPES = dict(input_ids=torch.int64, input_mask=torch.int64, segment_ids=torch.int64, lm_label_ids=torch.int64,
                is_next=torch.int64, image_feat=torch.float32, image_loc=torch.float32, image_target=torch.float32,
-               image_label=torch.int64, image_mask=torch.int64, masked_label=torch.int64)
+               image_label=torch.int64, image_mask=torch.int64, masked_label=torch.int64, overlaps=torch.float32)
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+BATCH_SEED_STRIDE = 0xD1B54A32D192ED03
+
+
+def batch_seed(seed, i):
+    """Seed of batch i of a run seeded with `seed`: the splitmix64 finaliser (all 64 bits) of
+    ``seed + (i + 1) * 0xD1B54A32D192ED03`` (mod 2^64). A pure function of (seed, i), so a restarted run reproduces its masks.
+    The kernel hashes ``seed + index * 0x9E3779B97F4A7C15``: two seeds a small multiple of that stride apart would draw the
+    same mask shifted by a few sites (ops._chunk_seed records that bug), which is why the per-batch term goes through the full
+    mixer instead of being added to the seed (tests/test_mask_batch.py checks batches 0 .. 63 pairwise)."""
+    z = (int(seed) + (int(i) + 1) * BATCH_SEED_STRIDE) & _MASK64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return z ^ (z >> 31)
+
+
+class Masking(object):
+    """Settings and batch counter of the device-side masking. The g-th batch masked through this object - counted from
+    `first_batch`, over every iteration of every DeviceBatchPipeline that holds it - is masked with ``batch_seed(seed, g)``:
+    a pure function of (seed, global batch index). The count runs on across iterations, so a second pass over the same
+    source draws new masks (``next_batch`` is where it stands); a run that restarts at global batch k passes first_batch=k
+    and repeats the masks of the original run from there."""
+
+    def __init__(self, seed, vocab_size, mask_token_id, p_select=0.15, first_batch=0):
+        if not 0.0 <= float(p_select) <= 1.0:
+            raise ValueError("p_select must lie in [0, 1], got %r" % (p_select,))
+        if int(vocab_size) <= 0 or not 0 <= int(mask_token_id) < int(vocab_size):
+            raise ValueError("mask_token_id %r is not an id of a vocabulary of %r" % (mask_token_id, vocab_size))
+        self.seed, self.vocab_size, self.mask_token_id = int(seed) & _MASK64, int(vocab_size), int(mask_token_id)
+        self.p_select, self.first_batch = float(p_select), int(first_batch)
+        self.next_batch = self.first_batch
+
+    def batch_seed(self, i):
+        """Seed of the i-th batch after `first_batch` (no state is touched)."""
+        return batch_seed(self.seed, self.first_batch + i)
+
+    def next_seed(self):
+        """Seed of global batch `next_batch`; advances the count."""
+        g = self.next_batch
+        self.next_batch = g + 1
+        return batch_seed(self.seed, g)
+
+
+def unmasked_preprocess(cls):
+    """A subclass of `cls` (a class shaped like the reference's BertPreprocessBatch) whose workers select nothing: its
+    samples reach the pipeline unmasked, in RAW_UNMASKED_FIELDS layout. Only the signatures of the two overridden methods
+    are relied on; negative captions and tokenisation stay with `cls`."""
+
+    class Unmasked(cls):
+        def random_word(self, tokens, tokenizer, is_next):
+            return tokens, [-1] * len(tokens)
+
+        def random_region(self, image_feat, image_loc, num_boxes, is_next, overlaps):
+            regions = image_feat.shape[0]
+            given = np.asarray(overlaps, dtype=np.float32)
+            padded = np.zeros((regions, regions), dtype=np.float32)
+            r, c = min(regions, given.shape[0]), min(regions, given.shape[1])
+            padded[:r, :c] = given[:r, :c]
+            return image_feat, image_loc, [-1] * int(num_boxes), padded
+
+    Unmasked.__name__ = "Unmasked" + cls.__name__
+    Unmasked.__qualname__ = Unmasked.__name__
+    return Unmasked
+
+
+def mask_batch(raw, seed, vocab_size, mask_token_id, p_select=0.15, inplace=True):
+    """raw: dict of DEVICE tensors named as RAW_UNMASKED_FIELDS (unmasked worker output). Draws the MLM and region masks
+    (include/vilbert_hip_inputs.h states the rule) and returns the dict `finish_batch` takes. Two native launches on the
+    current stream, no torch arithmetic. inplace=True rewrites the buffers of `raw` (input_ids, lm_label_ids, image_label,
+    the selected rows of image_feat); inplace=False leaves every tensor of `raw` as it is. image_target is passed through
+    untouched in both (the reference copies it before it masks)."""
+    feat = raw["image_feat"]
+    if feat.dim() != 3:
+        raise RuntimeError("image_feat must be [batch, regions, feat_dim]")
+    B, R, F = feat.shape
+    ids = raw["input_ids"]
+    if ids.dim() != 2 or ids.shape[0] != B:
+        raise RuntimeError("input_ids must be [batch, tokens]")
+    T = ids.shape[1]
+    dev = feat.device
+
+    def i64(name, shape):
+        t = raw[name]
+        if tuple(t.shape) != shape:
+            raise RuntimeError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
+        return N.dev_i64(t, name)
+
+    ov = raw["overlaps"]
+    if tuple(ov.shape) != (B, R, R) or not ov.is_contiguous() or not feat.is_contiguous():
+        raise RuntimeError("overlaps / image_feat: expected contiguous tensors of shape %s / %s, got %s / %s"
+                           % ((B, R, R), (B, R, F), tuple(ov.shape), tuple(feat.shape)))
+
+    def out_i64(name, shape):
+        t = raw.get(name) if inplace else None
+        if t is None or tuple(t.shape) != shape or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+            t = torch.empty(shape, dtype=torch.int64, device=dev)
+        return t
+
+    out_ids, lm, ilab = out_i64("input_ids", (B, T)), out_i64("lm_label_ids", (B, T)), out_i64("image_label", (B, R))
+    masked = torch.empty(B, R, dtype=torch.int64, device=dev)
+    zero_row = torch.empty(B, R, dtype=torch.uint8, device=dev)
+    a = N.MaskArgs()
+    a.batch, a.tokens, a.regions = B, T, R
+    a.vocab_size, a.mask_token_id, a.p_select, a.seed = int(vocab_size), int(mask_token_id), float(p_select), int(seed) & _MASK64
+    a.input_ids, a.input_mask, a.image_mask = i64("input_ids", (B, T)), i64("input_mask", (B, T)), i64("image_mask", (B, R))
+    a.overlaps = N.dev_f32(ov, "overlaps")
+    a.out_input_ids, a.lm_label_ids, a.image_label = out_ids.data_ptr(), lm.data_ptr(), ilab.data_ptr()
+    a.masked_label, a.zero_row = masked.data_ptr(), zero_row.data_ptr()
+    N.check(N.lib().vbi_concap_mask_batch(N.stream_ptr(), ctypes.byref(a)), "vbi_concap_mask_batch")
+    out_feat = feat if inplace else torch.empty_like(feat)
+    N.check(N.lib().vbi_zero_rows(N.stream_ptr(), B * R, F, N.dev_f32(feat, "image_feat"), F, zero_row.data_ptr(),
+                                  None if inplace else out_feat.data_ptr(), F), "vbi_zero_rows")
+    out = {n: raw[n] for n in RAW_FIELDS if n != "masked_label"}
+    out.update(input_ids=out_ids, lm_label_ids=lm, image_label=ilab, image_feat=out_feat, masked_label=masked)
+    return out
 
 
 def finish_batch(raw, objective=0):
@@ -96,10 +221,17 @@ class DeviceBatchPipeline(object):
     (Staging from a background thread was measured and is slower: the step's ~1500 kernel launches are
     Python-side work and lose more to GIL hand-offs than the overlap wins - 161 vs 137 ms per step at batch
     256.) The id / mask / target tensors of a yielded batch alias the slot's device buffers: they stay valid
-    until the caller asks for batch i + depth - 1 (do not keep them across iterations)."""
+    until the caller asks for batch i + depth - 1 (do not keep them across iterations).
 
-    def __init__(self, source, device, objective=0, depth=2, staging=None):
+    masking=None: the source masks (the reference's workers), as above. masking=Masking(...): the source yields UNMASKED
+    batches in RAW_UNMASKED_FIELDS order (``unmasked_preprocess`` makes such a worker class) and every batch is masked on the
+    compute stream by ``mask_batch`` with ``masking.next_seed()`` before it is finished: the Masking object counts the batches
+    across iterations (and across pipelines that share it), so each pass over a source draws new masks."""
+
+    def __init__(self, source, device, objective=0, depth=2, staging=None, masking=None):
         self.source, self.device, self.objective = source, torch.device(device), int(objective)
+        self.masking = masking
+        self.fields = RAW_FIELDS if masking is None else RAW_UNMASKED_FIELDS
         self.copy_stream = torch.cuda.Stream(device=self.device)
         self.slots = [_Slot() for _ in range(max(2, depth))]
         # "pinned": numpy -> pinned host buffer -> asynchronous DMA.  "direct": hand the pageable numpy memory to
@@ -112,10 +244,14 @@ class DeviceBatchPipeline(object):
             slot.copied.synchronize()                       # pinned buffers free again (long done)
         if slot.released is not None:
             self.copy_stream.wait_event(slot.released)      # device buffers free once that step has run
-        fields = dict(zip(RAW_FIELDS, batch[:len(RAW_FIELDS)]))
-        slot.extra = tuple(batch[len(RAW_FIELDS):])
+        fields = dict(zip(self.fields, batch[:len(self.fields)]))
+        slot.extra = tuple(batch[len(self.fields):])
         with torch.cuda.stream(self.copy_stream):
-            for name in RAW_FIELDS:
+            for name in self.fields:
+                if self.masking is not None and name in ("lm_label_ids", "image_label"):
+                    # all -1 from an unmasked source and never read: mask_batch writes every element of the device buffer
+                    slot.ensure(name, np.shape(fields[name]), _DTYPES[name], self.device)
+                    continue
                 arr = np.ascontiguousarray(fields[name])
                 h, d = slot.ensure(name, arr.shape, _DTYPES[name], self.device)
                 if self.staging == "direct" and arr.dtype == h.numpy().dtype:
@@ -139,7 +275,10 @@ class DeviceBatchPipeline(object):
             cur.wait_event(slot.copied)
             for t in slot.dev.values():
                 t.record_stream(cur)      # allocated on the copy stream, read by kernels of the compute stream
-            out = finish_batch(slot.dev, self.objective)
+            raw, m = slot.dev, self.masking
+            if m is not None:
+                raw = mask_batch(raw, m.next_seed(), m.vocab_size, m.mask_token_id, m.p_select, inplace=True)
+            out = finish_batch(raw, self.objective)
             yield out + slot.extra
             slot.released = torch.cuda.Event()
             slot.released.record(torch.cuda.current_stream(self.device))   # after the caller's step
