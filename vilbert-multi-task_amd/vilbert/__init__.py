@@ -121,3 +121,16 @@ def _install_optimization_finder():
 
 
 _install_optimization_finder()
+
+
+# --- the device-side batch builder of the fine-tuning tasks, by name ----------------------------------------------------
+# `from vilbert import TaskBatchPipeline` (vilbert/task_pipeline.py). Resolved on first use: importing the package loads
+# neither torch nor the native library.
+_TASK_PIPELINE_NAMES = ("raw_item", "pack_task_samples", "finish_task_batch", "dense_target", "TaskBatchPipeline")
+
+
+def __getattr__(name):
+    if name in _TASK_PIPELINE_NAMES:
+        from . import task_pipeline
+        return getattr(task_pipeline, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -299,6 +299,19 @@ class MaskArgs(ctypes.Structure):
     ]
 
 
+class TaskBatchArgs(ctypes.Structure):
+    """vbd_task_batch (104 bytes; include/vilbert_hip_task_inputs.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("max_regions", ctypes.c_int32), ("feat_dim", ctypes.c_int32),
+        ("iou_floor", ctypes.c_float),
+        ("total_rows", ctypes.c_int64),
+        ("feat", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+        ("image_wh", ctypes.c_void_p), ("mean_rows", ctypes.c_void_p), ("ref_box", ctypes.c_void_p),
+        ("out_feat", ctypes.c_void_p), ("out_spatials", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
+        ("out_iou", ctypes.c_void_p),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -448,6 +461,13 @@ INPUT_SIGNATURES = {
     "vbi_zero_rows": (ctypes.c_int, [_P, _I64, _I32, _P, _I64, _P, _P, _I64]),
 }
 
+# include/vilbert_hip_task_inputs.h (device-side building of a fine-tuning batch from packed regions; prefix vbd_), mirrored
+# one to one (checked by tests/test_task_batch.py)
+TASK_INPUT_SIGNATURES = {
+    "vbd_task_finish_batch": (ctypes.c_int, [_P, ctypes.POINTER(TaskBatchArgs)]),
+    "vbd_dense_target": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _I64]),
+}
+
 _lib = None
 
 
@@ -463,7 +483,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(OPT_SIGNATURES.items())
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
                                   + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
-                                  + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())):
+                                  + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())
+                                  + list(TASK_INPUT_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:
