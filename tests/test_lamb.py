@@ -25,13 +25,11 @@ import pytest
 import torch
 
 import lamb_restatement as lamb
+from optim_helpers import C_TYPES as _C_TYPES, header_text, native, prototypes  # noqa: F401 (native: a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "vilbert-multi-task_amd")
 HEADER = os.path.join(ROOT, "include", "vilbert_hip_lamb.h")
-
-_C_TYPES = {"void*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-            "int": ctypes.c_int}
 
 # (adam_w_mode, bias_correction, grad_averaging) -> measured fp32 - float64 distance of the restatement on the case of
 # tests/lamb_restatement.py: (parameters, exp_avg, exp_avg_sq). tests/test_lamb_gpu.py allows the kernels 4 x these.
@@ -57,27 +55,11 @@ def worst(got, want):
 
 
 def _header_text():
-    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return header_text(HEADER)
 
 
 def _prototypes():
-    """name -> (return ctype, [argument ctypes]) parsed from the header text; every pointer is a plain address."""
-    out = {}
-    for ret, name, args in re.findall(r"\b(int64_t|int)\s+(vbl_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header_text()):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            types.append(ctypes.c_void_p if "*" in a else _C_TYPES[a.replace("const ", "").split()[0]])
-        out[name] = (_C_TYPES[ret], types)
-    return out
-
-
-@pytest.fixture(scope="module")
-def native():
-    import __graft_entry__
-    __graft_entry__.build()
-    from vilbert import _native
-    return _native
+    return prototypes(HEADER, "vbl_")
 
 
 def test_header_declares_the_lamb_entry_points_and_leaves_the_other_headers_alone():

@@ -18,26 +18,15 @@ import pytest
 import torch
 
 import lamb_restatement as lamb
+from optim_helpers import DEV, bits_equal as _bits_equal, device_grad, device_params
+from optim_helpers import leave_no_workspace_slices_behind  # noqa: F401 (an autouse fixture: the captured step and the model of this file bring streams of their own)
 from test_lamb import DIST, options, worst
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 CHUNK = lamb.CHUNK
 N_CHUNKS = 1 + 1 + 2 + 3 + 1 + 1 + 1 + 1
 WALK = [i for g in lamb.GROUPS for i in g["idx"]]           # the order step() walks the tensors in: groups, then parameters
 IDS = lambda c: "%s-%s-%s" % ("adamw" if c[0] else "l2", "corrected" if c[1] else "plain", "averaged" if c[2] else "summed")
-
-
-@pytest.fixture(autouse=True)
-def _leave_no_workspace_slices_behind():
-    """As in tests/test_optim_clip_gpu.py: the captured step and the model of this file bring streams of their own; the
-    deterministic workspace is re-registered after each test so that later tests of the process find its slices free."""
-    yield
-    from vilbert import _native
-    if _native.deterministic_enabled() and _native._DET["ws"]:
-        torch.cuda.synchronize()
-        _native.set_deterministic(False)
-        _native.set_deterministic(True)
 
 
 @pytest.fixture(scope="module")
@@ -47,23 +36,12 @@ def case():
     return {"p0": p0, "grads": grads}
 
 
-def _odd(t):
-    """A device copy of `t` one element into its storage: data_ptr % 16 == 4."""
-    base = torch.empty(t.numel() + 1, device=DEV)
-    view = base[1:]
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4
-    return view
-
-
 def _device_params(p0):
-    return [torch.nn.Parameter(_odd(t) if i == lamb.ODD else t.to(DEV)) for i, t in enumerate(p0)]
+    return device_params(p0, lamb.ODD)
 
 
 def _device_grad(t, i):
-    if t is None:
-        return None
-    return _odd(t) if i == lamb.ODD else t.to(DEV)
+    return device_grad(t, i == lamb.ODD)
 
 
 def _make(cls, ps, groups=lamb.GROUPS, **kw):
@@ -83,10 +61,6 @@ def _run_native(cls, p0, grads, groups=lamb.GROUPS, factor=lamb.lr_factor, **kw)
         opt.step()
     torch.cuda.synchronize()
     return opt, ps
-
-
-def _bits_equal(a, b):
-    return torch.equal(a.detach().contiguous().view(torch.int32), b.detach().contiguous().view(torch.int32))
 
 
 def _state(opt, ps):

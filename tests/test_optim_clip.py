@@ -12,32 +12,14 @@ import subprocess
 import pytest
 import torch
 
+from optim_helpers import native, prototypes  # noqa: F401 (native: a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXT_HEADER = os.path.join(ROOT, "include", "vilbert_hip_ext.h")
 
-_C_TYPES = {"void*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-            "int": ctypes.c_int}
-
 
 def _prototypes():
-    """name -> (return ctype, [argument ctypes]) parsed from the header text; every pointer is a plain address."""
-    text = re.sub(r"/\*.*?\*/", "", open(EXT_HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int64_t|int)\s+(vbx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            types.append(ctypes.c_void_p if "*" in a else _C_TYPES[a.replace("const ", "").split()[0]])
-        out[name] = (_C_TYPES[ret], types)
-    return out
-
-
-@pytest.fixture(scope="module")
-def native():
-    import __graft_entry__
-    __graft_entry__.build()
-    from vilbert import _native
-    return _native
+    return prototypes(EXT_HEADER, "vbx_")
 
 
 def test_extension_header_declares_the_three_entry_points():

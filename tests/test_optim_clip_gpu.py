@@ -1,5 +1,5 @@
 """Fused global-norm clipping, gradient scale and overflow-safe step of the native AdamW (csrc/optimizer.hip:
-grad_sumsq_kernel, grad_norm_finish_kernel, adamw_kernel<true>) on the GPU: norm accuracy, reproducibility, bit-identity with
+grad_sumsq_kernel, grad_norm_finish_kernel, adamw_kernel) on the GPU: norm accuracy, reproducibility, bit-identity with
 the plain step where the coefficient is 1 or a power of two, the clipped trajectory against torch.nn.utils.clip_grad_norm_ +
 the plain native step, skipped non-finite steps, every construction order of optimizer and DistributedDataParallel, foreign
 gradients, and the captured bf16 step. A non-finite gradient here is an ordinary value written with fill_."""
@@ -10,10 +10,11 @@ import pytest
 import torch
 import torch.distributed as dist
 
+from optim_helpers import DEV, bits_equal as _bits_equal
+from optim_helpers import leave_no_workspace_slices_behind  # noqa: F401 (an autouse fixture: the models, wrappers and captured steps of this file bring streams of their own)
 from oracle import synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 NAMES = ["input_ids", "image_feat", "image_loc", "token_type_ids", "attention_mask", "image_attention_mask",
          "masked_lm_labels", "image_label", "image_target", "next_sentence_label"]
 # sizes of the issue's mixed set; the oddly offset view (data_ptr % 16 == 4, scalar path of every kernel) is added by _params
@@ -21,21 +22,6 @@ SIZES = [1, 5, 4097, 3 * 65536 + 3]
 ODD = 4099
 # tests/test_optim.py::test_native_adamw_matches_the_torch_derived_golden_trajectories: |p - want| <= 3e-6 * max(1, max |want|)
 TRAJ_TOL = 3e-6
-
-
-@pytest.fixture(autouse=True)
-def _leave_no_workspace_slices_behind():
-    """The deterministic workspace hands its 8 slices to the first 8 streams that run a split launch and keeps that
-    assignment for as long as the same buffer stays registered (csrc/det_workspace.hip) - a ninth stream falls back to
-    atomics. The models, data-parallel wrappers and captured steps of this file bring streams of their own; switching
-    the setting off and on again after each test re-registers the same buffer with an empty assignment, so that the
-    tests that run later in the same process find the slices free. (No graph of this file outlives its test.)"""
-    yield
-    from vilbert import _native
-    if _native.deterministic_enabled() and _native._DET["ws"]:
-        torch.cuda.synchronize()
-        _native.set_deterministic(False)
-        _native.set_deterministic(True)
 
 
 def _params(seed=3):
@@ -73,10 +59,6 @@ def _clone_params(ps):
 
 def _norm64(grads):
     return torch.sqrt(sum((g.double() ** 2).sum() for g in grads)).item()
-
-
-def _bits_equal(a, b):
-    return torch.equal(a.detach().contiguous().view(torch.int32), b.detach().contiguous().view(torch.int32))
 
 
 def _assert_state_bits(opt_a, ps_a, opt_b, ps_b, what):

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import radam_restatement as rr
+from optim_helpers import C_TYPES as _C_TYPES, native, prototypes  # noqa: F401 (native: a fixture)
 from oracle import ref_loader
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,9 +27,6 @@ PKG = os.path.join(ROOT, "vilbert-multi-task_amd")
 OPT_HEADER = os.path.join(ROOT, "include", "vilbert_hip_optim.h")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "radam_trajectory.npz")
 needs_reference = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not present")
-
-_C_TYPES = {"void*": ctypes.c_void_p, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-            "int": ctypes.c_int}
 
 # Distance between the restatement run in fp32 and in float64 on the fixture's case (max |p32 - p64| over the final
 # parameters of both variants, measured: 2.83e-7; parameters are O(1), 12 steps). The recorded fp32 trajectory of the
@@ -39,24 +37,7 @@ GOLDEN_BOUND = 4 * GOLDEN_FP32_DISTANCE
 
 
 def _prototypes():
-    """name -> (return ctype, [argument ctypes]) parsed from the header text; every pointer is a plain address."""
-    text = re.sub(r"/\*.*?\*/", "", open(OPT_HEADER).read(), flags=re.S)
-    out = {}
-    for ret, name, args in re.findall(r"\b(int64_t|int)\s+(vbo_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
-        types = []
-        for a in args.split(","):
-            a = a.strip()
-            types.append(ctypes.c_void_p if "*" in a else _C_TYPES[a.replace("const ", "").split()[0]])
-        out[name] = (_C_TYPES[ret], types)
-    return out
-
-
-@pytest.fixture(scope="module")
-def native():
-    import __graft_entry__
-    __graft_entry__.build()
-    from vilbert import _native
-    return _native
+    return prototypes(OPT_HEADER, "vbo_")
 
 
 @pytest.fixture(scope="module")

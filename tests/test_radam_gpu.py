@@ -20,9 +20,9 @@ import pytest
 import torch
 
 import radam_restatement as rr
+from optim_helpers import DEV, bits_equal as _bits_equal, device_grad, device_params
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 CHUNK = 65536
 SIZES = [1, 3, 4, 1021, CHUNK + 5]
 ODD = 37
@@ -60,26 +60,12 @@ def case():
     return out
 
 
-def _odd(t):
-    """A device copy of `t` one element into its storage: data_ptr % 16 == 4."""
-    base = torch.empty(t.numel() + 1, device=DEV)
-    view = base[1:]
-    view.copy_(t)
-    assert view.data_ptr() % 16 == 4
-    return view
-
-
 def _device_params(p0, odd_last=True):
-    ps = [torch.nn.Parameter(t.to(DEV)) for t in (p0[:-1] if odd_last else p0)]
-    if odd_last:
-        ps.append(torch.nn.Parameter(_odd(p0[-1])))
-    return ps
+    return device_params(p0, len(p0) - 1 if odd_last else None)
 
 
 def _device_grad(t, i, n_tensors, odd_last=True):
-    if t is None:
-        return None
-    return _odd(t) if (odd_last and i == n_tensors - 1) else t.to(DEV)
+    return device_grad(t, odd_last and i == n_tensors - 1)
 
 
 def _make(cls, ps, groups=GROUPS, betas=BETAS, **kw):
@@ -103,10 +89,6 @@ def _run_native(cls, p0, grads, groups=GROUPS, lr_factor=rr.golden_lr_factor, od
 
 def _worst(got, want):
     return max(float((a.detach().cpu().double() - b.double()).abs().max()) for a, b in zip(got, want))
-
-
-def _bits_equal(a, b):
-    return torch.equal(a.detach().contiguous().view(torch.int32), b.detach().contiguous().view(torch.int32))
 
 
 @pytest.mark.parametrize("name", ["radam", "plain"])

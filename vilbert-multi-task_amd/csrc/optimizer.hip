@@ -10,72 +10,42 @@
 // Global-norm clipping, a gradient scale and the skip of a non-finite step ride on the same tables (vilbert_hip_ext.h):
 //   grad_sumsq_kernel        one block per chunk -> one fp32 partial sum of squares per chunk (4 B read per parameter)
 //   grad_norm_finish_kernel  one block: partials -> {sum of squares, norm, coef, finite flag, skipped steps} on the device
-//   adamw_kernel<true>       the update with every gradient multiplied by coef on load; no store at all when the step is skipped
+//   adamw_kernel             given that state, the update with every gradient multiplied by coef on load; no store at all when
+//                            the step is skipped
 // No atomics and a fixed summation order everywhere: the same gradients give the same bits. The coefficient never visits the
 // host, so the three launches are graph-capturable. The gradients themselves are only read.
 //
 // Multi-tensor RAdam step (vilbert_hip_optim.h; the reference's vilbert/optimization.py:55-98, `--optim RAdam` of train_tasks.py):
-//   radam_kernel             the same chunk walk over the same tables; the per-tensor hyper-parameters - step size, rectified
-//                            flag, lr * wd - come from a table of their own the host computes in double, the optional state of
-//                            grad_norm_finish_kernel scales the gradients and skips an overflowed step as in adamw_kernel<true>
+//   radam_kernel             the per-tensor hyper-parameters - step size, rectified flag, lr * wd - come from a table of their
+//                            own the host computes in double
+//
+// Every kernel but grad_norm_finish_kernel is the chunk walk of optim_walk.h around its element function: one block per chunk,
+// 16-byte accesses where the tensor's base pointers allow them, the optional state of the norm pass read once per block.
 #include <cmath>
 
-#include "common.h"
+#include "optim_walk.h"
 #include "../../include/vilbert_hip_optim.h"
 
 namespace {
 
-// SCALED = false is the plain step (vb_adamw_step; `state` / `skip` unused). SCALED = true reads the coefficient and the
-// finite flag once per block from the state grad_norm_finish_kernel wrote and multiplies every gradient by it on load; a block
-// of a skipped step returns before any store.
-template <bool SCALED>
+using namespace optim_walk;
+
+__device__ __forceinline__ void adamw_element(const vb_adamw_tensor& t, float g, float& p, float& m, float& v) {
+    m = m * t.beta1 + (1.0f - t.beta1) * g;
+    v = v * t.beta2 + (1.0f - t.beta2) * g * g;
+    p -= t.step_size * (m / (sqrtf(v) + t.eps));
+    if (t.decay > 0.f) p -= t.decay * p;
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(const vb_adamw_tensor* __restrict__ tab,
                                                     const int32_t* __restrict__ chunk_tensor,
                                                     const int64_t* __restrict__ chunk_off, int chunk_elems,
                                                     const float* __restrict__ state, int skip) {
-    float coef = 1.0f;
-    if constexpr (SCALED) {
-        if (skip && state[VB_GRAD_STATE_FINITE] == 0.f) return;
-        coef = state[VB_GRAD_STATE_COEF];
-    }
-    const vb_adamw_tensor t = tab[chunk_tensor[blockIdx.x]];
-    const long off = chunk_off[blockIdx.x];
-    const long end = min((long)t.numel, off + chunk_elems);
-    const float b1 = t.beta1, b2 = t.beta2, c1 = 1.0f - t.beta1, c2 = 1.0f - t.beta2;
-    float* __restrict__ p = t.param;
-    const float* __restrict__ g = t.grad;
-    float* __restrict__ m = t.exp_avg;
-    float* __restrict__ v = t.exp_avg_sq;
-    // 16-byte accesses need all four base pointers 16-byte aligned (chunk offsets are multiples of 4 elements);
-    // a tensor that is an oddly offset view takes the scalar loop for its whole chunk
-    const bool vec_ok = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                          reinterpret_cast<uintptr_t>(v)) & 15u) == 0;
-    const long n4 = vec_ok ? (end - off) >> 2 : 0;
-    for (long i = threadIdx.x; i < n4; i += 256) {
-        const long e = off + 4 * i;
-        f32x4 pp = *reinterpret_cast<f32x4*>(p + e);
-        f32x4 gg = *reinterpret_cast<const f32x4*>(g + e);
-        if constexpr (SCALED) gg *= coef;
-        f32x4 mm = *reinterpret_cast<f32x4*>(m + e), vv = *reinterpret_cast<f32x4*>(v + e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            mm[k] = mm[k] * b1 + c1 * gg[k];
-            vv[k] = vv[k] * b2 + c2 * gg[k] * gg[k];
-            pp[k] -= t.step_size * (mm[k] / (sqrtf(vv[k]) + t.eps));
-            if (t.decay > 0.f) pp[k] -= t.decay * pp[k];
-        }
-        *reinterpret_cast<f32x4*>(p + e) = pp;
-        *reinterpret_cast<f32x4*>(m + e) = mm;
-        *reinterpret_cast<f32x4*>(v + e) = vv;
-    }
-    for (long e = off + 4 * n4 + threadIdx.x; e < end; e += 256) {
-        float gg = g[e];
-        if constexpr (SCALED) gg *= coef;
-        const float mm = m[e] * b1 + c1 * gg, vv = v[e] * b2 + c2 * gg * gg;
-        float pp = p[e] - t.step_size * (mm / (sqrtf(vv) + t.eps));
-        if (t.decay > 0.f) pp -= t.decay * pp;
-        p[e] = pp; m[e] = mm; v[e] = vv;
-    }
+    float coef;
+    if (!grad_state(state, skip, coef)) return;
+    const Chunk c = chunk_of_block(tab, chunk_tensor, chunk_off, chunk_elems);
+    walk<P | G | M | V, P | M | V, ALIGN_ALL>(
+        c, coef, [&](int, float& p, float g, float& m, float& v) { adamw_element(c.t, g, p, m, v); });
 }
 
 // One element of the RAdam step, in the reference's order: second moment, first moment, decay on the OLD value, then the
@@ -88,78 +58,29 @@ __device__ __forceinline__ void radam_element(const vbo_radam_scalars& h, float 
     else p -= h.step_size * m;
 }
 
-// `state` == nullptr is the plain step; otherwise the coefficient and the finite flag are read once per block (uniform
-// branches) and a block of a skipped step returns before any store. coef = 1 multiplies exactly, so one kernel serves both.
 __global__ __launch_bounds__(256) void radam_kernel(const vb_adamw_tensor* __restrict__ tab,
                                                     const vbo_radam_scalars* __restrict__ scalars,
                                                     const int32_t* __restrict__ chunk_tensor,
                                                     const int64_t* __restrict__ chunk_off, int chunk_elems,
                                                     const float* __restrict__ state, int skip) {
-    float coef = 1.0f;
-    if (state != nullptr) {
-        if (skip && state[VB_GRAD_STATE_FINITE] == 0.f) return;
-        coef = state[VB_GRAD_STATE_COEF];
-    }
-    const int ti = chunk_tensor[blockIdx.x];
-    const vb_adamw_tensor t = tab[ti];
-    const vbo_radam_scalars h = scalars[ti];
-    const long off = chunk_off[blockIdx.x];
-    const long end = min((long)t.numel, off + chunk_elems);
-    float* __restrict__ p = t.param;
-    const float* __restrict__ g = t.grad;
-    float* __restrict__ m = t.exp_avg;
-    float* __restrict__ v = t.exp_avg_sq;
-    // as adamw_kernel: 16-byte accesses only where all four base pointers allow them (chunk offsets are multiples of 4)
-    const bool vec_ok = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                          reinterpret_cast<uintptr_t>(v)) & 15u) == 0;
-    const long n4 = vec_ok ? (end - off) >> 2 : 0;
-    for (long i = threadIdx.x; i < n4; i += 256) {
-        const long e = off + 4 * i;
-        f32x4 pp = *reinterpret_cast<f32x4*>(p + e);
-        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e) * coef;
-        f32x4 mm = *reinterpret_cast<f32x4*>(m + e), vv = *reinterpret_cast<f32x4*>(v + e);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float pk = pp[k], mk = mm[k], vk = vv[k];
-            radam_element(h, gg[k], pk, mk, vk);
-            pp[k] = pk; mm[k] = mk; vv[k] = vk;
-        }
-        *reinterpret_cast<f32x4*>(p + e) = pp;
-        *reinterpret_cast<f32x4*>(m + e) = mm;
-        *reinterpret_cast<f32x4*>(v + e) = vv;
-    }
-    for (long e = off + 4 * n4 + threadIdx.x; e < end; e += 256) {
-        float pp = p[e], mm = m[e], vv = v[e];
-        radam_element(h, g[e] * coef, pp, mm, vv);
-        p[e] = pp; m[e] = mm; v[e] = vv;
-    }
+    float coef;
+    if (!grad_state(state, skip, coef)) return;
+    const Chunk c = chunk_of_block(tab, chunk_tensor, chunk_off, chunk_elems);
+    const vbo_radam_scalars h = scalars[c.ti];
+    walk<P | G | M | V, P | M | V, ALIGN_ALL>(
+        c, coef, [&](int, float& p, float g, float& m, float& v) { radam_element(h, g, p, m, v); });
 }
 
-// Sum of squares of one chunk of one gradient. Fixed order: four per-thread accumulators (one per vector lane; the scalar
-// path uses the first), each a chain of at most chunk_elems / 1024 = 64 adds, combined lane 0..3, then the xor tree of the
-// wave, then waves 0..3 through LDS.
+// Sum of squares of one chunk of one gradient: per-lane chains of at most chunk_elems / 1024 = 64 fused multiply-adds (fmaf
+// spelled out: the unrolled loop keeps them fused in every lane), then the fixed order of optim_walk.h.
 __global__ __launch_bounds__(256) void grad_sumsq_kernel(const vb_adamw_tensor* __restrict__ tab,
                                                          const int32_t* __restrict__ chunk_tensor,
                                                          const int64_t* __restrict__ chunk_off, int chunk_elems,
                                                          float* __restrict__ partials) {
-    const int ti = chunk_tensor[blockIdx.x];
-    const float* __restrict__ g = tab[ti].grad;
-    const long off = chunk_off[blockIdx.x];
-    const long end = min((long)tab[ti].numel, off + chunk_elems);
-    const bool vec_ok = (reinterpret_cast<uintptr_t>(g) & 15u) == 0;
-    const long n4 = vec_ok ? (end - off) >> 2 : 0;
+    const Chunk c = chunk_of_block(tab, chunk_tensor, chunk_off, chunk_elems);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-    for (long i = threadIdx.x; i < n4; i += 256) {
-        const f32x4 gg = *reinterpret_cast<const f32x4*>(g + off + 4 * i);
-        acc += gg * gg;
-    }
-    for (long e = off + 4 * n4 + threadIdx.x; e < end; e += 256) acc[0] += g[e] * g[e];
-    const float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
-    __shared__ float wave_part[4];
-    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+    walk<G, 0, ALIGN_GRAD, 4>(c, 1.0f, [&](int lane, float&, float g, float&, float&) { acc[lane] = fmaf(g, g, acc[lane]); });
+    block_sum({lane_sum(acc)}, partials + blockIdx.x);
 }
 
 // partials -> state. Thread t adds partials[t], partials[t + 256], ... in index order, then a fixed binary tree over the 256
@@ -198,14 +119,26 @@ __global__ __launch_bounds__(256) void grad_norm_finish_kernel(const float* __re
 
 }  // namespace
 
-extern "C" int vb_adamw_step(void* stream, int32_t n_chunks, const vb_adamw_tensor* table,
-                             const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems) {
-    if (table == nullptr || chunk_tensor == nullptr || chunk_off == nullptr || n_chunks <= 0) return VB_E_BADARG;
-    if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
-    hipLaunchKernelGGL(adamw_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table,
-                       chunk_tensor, chunk_off, chunk_elems, static_cast<const float*>(nullptr), 0);
+// `state` == nullptr is the plain step
+static int launch_adamw(void* stream, int32_t n_chunks, const vb_adamw_tensor* table, const int32_t* chunk_tensor,
+                        const int64_t* chunk_off, int32_t chunk_elems, const float* state, int32_t skip_nonfinite) {
+    if (int e = check_tables(n_chunks, table, chunk_tensor, chunk_off, chunk_elems)) return e;
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table,
+                       chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite != 0 ? 1 : 0);
     VB_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vb_adamw_step(void* stream, int32_t n_chunks, const vb_adamw_tensor* table,
+                             const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems) {
+    return launch_adamw(stream, n_chunks, table, chunk_tensor, chunk_off, chunk_elems, nullptr, 0);
+}
+
+extern "C" int vbx_adamw_step_scaled(void* stream, int32_t n_chunks, const vb_adamw_tensor* table,
+                                     const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems,
+                                     const float* state, int32_t skip_nonfinite) {
+    if (state == nullptr) return VB_E_BADARG;
+    return launch_adamw(stream, n_chunks, table, chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite);
 }
 
 extern "C" int64_t vbx_grad_norm_workspace(int32_t n_chunks) { return n_chunks > 0 ? (int64_t)n_chunks : 0; }
@@ -213,11 +146,8 @@ extern "C" int64_t vbx_grad_norm_workspace(int32_t n_chunks) { return n_chunks >
 extern "C" int vbx_grad_norm(void* stream, int32_t n_chunks, const vb_adamw_tensor* table, const int32_t* chunk_tensor,
                              const int64_t* chunk_off, int32_t chunk_elems, float max_norm, float grad_scale,
                              int32_t skip_nonfinite, float* partials, float* state) {
-    if (table == nullptr || chunk_tensor == nullptr || chunk_off == nullptr || partials == nullptr || state == nullptr ||
-        n_chunks <= 0)
-        return VB_E_BADARG;
     if (!(max_norm >= 0.f) || !std::isfinite(max_norm) || !std::isfinite(grad_scale)) return VB_E_BADARG;
-    if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
+    if (int e = check_tables(n_chunks, table, chunk_tensor, chunk_off, chunk_elems, {partials, state})) return e;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)n_chunks), dim3(256), 0, st, table, chunk_tensor, chunk_off,
                        chunk_elems, partials);
@@ -228,24 +158,10 @@ extern "C" int vbx_grad_norm(void* stream, int32_t n_chunks, const vb_adamw_tens
     return 0;
 }
 
-extern "C" int vbx_adamw_step_scaled(void* stream, int32_t n_chunks, const vb_adamw_tensor* table,
-                                     const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems,
-                                     const float* state, int32_t skip_nonfinite) {
-    if (table == nullptr || chunk_tensor == nullptr || chunk_off == nullptr || state == nullptr || n_chunks <= 0)
-        return VB_E_BADARG;
-    if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
-    hipLaunchKernelGGL(adamw_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table,
-                       chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite != 0 ? 1 : 0);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
 extern "C" int vbo_radam_step(void* stream, int32_t n_chunks, const vb_adamw_tensor* table, const vbo_radam_scalars* scalars,
                               const int32_t* chunk_tensor, const int64_t* chunk_off, int32_t chunk_elems, const float* state,
                               int32_t skip_nonfinite) {
-    if (table == nullptr || scalars == nullptr || chunk_tensor == nullptr || chunk_off == nullptr || n_chunks <= 0)
-        return VB_E_BADARG;
-    if (chunk_elems <= 0 || chunk_elems % 4 != 0) return VB_E_ALIGN;
+    if (int e = check_tables(n_chunks, table, chunk_tensor, chunk_off, chunk_elems, {scalars})) return e;
     hipLaunchKernelGGL(radam_kernel, dim3((unsigned)n_chunks), dim3(256), 0, static_cast<hipStream_t>(stream), table, scalars,
                        chunk_tensor, chunk_off, chunk_elems, state, skip_nonfinite != 0 ? 1 : 0);
     VB_LAUNCH_CHECK();

@@ -44,6 +44,17 @@ def _check_clip_args(max_grad_norm, grad_scale):
         raise ValueError("Invalid grad_scale: {} - should be finite".format(grad_scale))
 
 
+def _check_adam_args(lr, betas, eps):
+    if lr < 0.0:
+        raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
+    if not 0.0 <= betas[0] < 1.0:
+        raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
+    if not 0.0 <= betas[1] < 1.0:
+        raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
+    if not 0.0 <= eps:
+        raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+
+
 class _MultiTensorOptimizer(Optimizer):
     """What the native optimizers share: the gradient arena, the launch tables (one vb_adamw_tensor row per tensor, chunk
     lists on the device, uploaded through pinned memory without a host synchronisation), the fused global-norm clipping /
@@ -195,12 +206,10 @@ class _MultiTensorOptimizer(Optimizer):
             ev.record()
             plan["events"][k] = ev
         if self._scaled():
-            partials, state = self._clip_buffers(plan, device, capturing)
+            partials, state = self._clip_buffers(plan, device)
             skip = int(self.skip_nonfinite)
-            N.check(N.lib().vbx_grad_norm(N.stream_ptr(), plan["n_chunks"], dev_tab.data_ptr(),
-                                          plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
-                                          self.max_grad_norm, self.grad_scale, skip, partials.data_ptr(), state.data_ptr()),
-                    "vbx_grad_norm")
+            N.check(N.lib().vbx_grad_norm(*self._table_args(plan), self.max_grad_norm, self.grad_scale, skip,
+                                          partials.data_ptr(), state.data_ptr()), "vbx_grad_norm")
             self._launch(plan, state, skip)
         else:
             self._launch(plan, None, 0)
@@ -208,16 +217,28 @@ class _MultiTensorOptimizer(Optimizer):
         del keep
         return loss
 
+    @classmethod
+    def _table_args(cls, plan, scalars=False):
+        """The leading arguments of every native entry point: stream, chunk count, tensor table (`scalars`: the class's
+        second table right behind it), chunk lists, chunk size."""
+        tables = (plan["dev_tab"].data_ptr(),) + ((cls._extra_ptr(plan),) if scalars else ())
+        return (N.stream_ptr(), plan["n_chunks"]) + tables + (plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(),
+                                                             CHUNK_ELEMS)
+
     def _scaled(self):
         return self.max_grad_norm > 0.0 or self.grad_scale != 1.0 or self.skip_nonfinite
 
-    def _clip_buffers(self, plan, device, capturing):
+    def _allocating(self, step, buffers):
+        """Fixed-address device buffers are allocated by the first eager step that needs them - never inside a capture."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("%s: the first %s of a plan allocates its %s and must run eagerly before a graph capture "
+                               "(GraphedTrainStep's warm-up does)" % (self._NAME, step, buffers))
+
+    def _clip_buffers(self, plan, device):
         """Fixed-address buffers of the norm pass: the per-chunk partial sums belong to the plan, the state (norm,
         coefficient, finite flag, skipped-step count) to the optimizer - the count survives a change of plan."""
         if self._grad_state is None or "partials" not in plan:
-            if capturing:
-                raise RuntimeError(self._NAME + ": the first clipped / scaled step of a plan allocates its buffers and must run "
-                                   "eagerly before a graph capture (GraphedTrainStep's warm-up does)")
+            self._allocating("clipped / scaled step", "buffers")
             if self._grad_state is None:
                 self._grad_state = torch.zeros(N.GRAD_STATE_FLOATS, dtype=torch.float32, device=device)
             plan["partials"] = torch.empty(int(N.lib().vbx_grad_norm_workspace(plan["n_chunks"])), dtype=torch.float32,
@@ -268,6 +289,18 @@ class _MultiTensorOptimizer(Optimizer):
             gi = plan["group_index"] = np.array([ids[id(g)] for _p, _st, g in entries], dtype=np.int64)
         return gi
 
+    def _hyper_columns(self, plan, entries, *switches):
+        """One float64 value per entry of lr, beta1, beta2, eps, weight_decay (through the group index) and of the tensor's
+        own step count, then one boolean per entry for every group key in `switches`. (vectorised: this runs on the host
+        once per step, ~530 rows)"""
+        gi = self._group_index(plan, entries)
+        groups = self.param_groups
+        cols = [[g["lr"] for g in groups], [g["betas"][0] for g in groups], [g["betas"][1] for g in groups],
+                [g["eps"] for g in groups], [g["weight_decay"] for g in groups]]
+        cols = [np.array(c, dtype=np.float64)[gi] for c in cols]
+        cols.append(np.fromiter((st["step"] for _p, st, _g in entries), dtype=np.float64, count=len(entries)))
+        return cols + [np.array([bool(g[k]) for g in groups])[gi] for k in switches]
+
     def prepare_replay(self):
         """Host side of one replay of a captured step (GraphedTrainStep): advances the step counts and rewrites the
         pinned table the captured copy node reads (learning-rate schedule, bias correction). The previous replay
@@ -292,38 +325,21 @@ class AdamW(_MultiTensorOptimizer):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True,
                  max_grad_norm=0.0, grad_scale=1.0, skip_nonfinite=False):
-        if lr < 0.0:
-            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
-        if not 0.0 <= eps:
-            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        _check_adam_args(lr, betas, eps)
         self._init_native(max_grad_norm, grad_scale, skip_nonfinite)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias)
         super(AdamW, self).__init__(params, defaults)
         self._init_plan()
 
     def _fill_hyper(self, plan, entries):
-        """(vectorised: this runs on the host once per step, ~530 rows)"""
-        tab, n = plan["tab"], len(entries)
-        gi = self._group_index(plan, entries)
-        groups = self.param_groups
-        lr = np.array([g["lr"] for g in groups], dtype=np.float64)[gi]
-        b1 = np.array([g["betas"][0] for g in groups], dtype=np.float64)[gi]
-        b2 = np.array([g["betas"][1] for g in groups], dtype=np.float64)[gi]
-        eps = np.array([g["eps"] for g in groups], dtype=np.float64)[gi]
-        wd = np.array([g["weight_decay"] for g in groups], dtype=np.float64)[gi]
-        corr = np.array([bool(g["correct_bias"]) for g in groups])[gi]
-        steps = np.fromiter((st["step"] for _p, st, _g in entries), dtype=np.float64, count=n)
+        tab = plan["tab"]
+        lr, b1, b2, eps, wd, steps, corr = self._hyper_columns(plan, entries, "correct_bias")
         step_size = np.where(corr, lr * np.sqrt(1.0 - b2 ** steps) / (1.0 - b1 ** steps), lr)
         tab["step_size"], tab["beta1"], tab["beta2"] = step_size, b1, b2
         tab["eps"], tab["decay"] = eps, lr * wd
 
     def _launch(self, plan, state, skip):
-        args = (N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), plan["chunk_tensor"].data_ptr(),
-                plan["chunk_off"].data_ptr(), CHUNK_ELEMS)
+        args = self._table_args(plan)
         if state is None:
             N.check(N.lib().vb_adamw_step(*args), "vb_adamw_step")
         else:
@@ -386,9 +402,8 @@ class PlainRAdam(_MultiTensorOptimizer):
         extra["rectified"] = rect
 
     def _launch(self, plan, state, skip):
-        N.check(N.lib().vbo_radam_step(N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), self._extra_ptr(plan),
-                                       plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
-                                       None if state is None else state.data_ptr(), skip), "vbo_radam_step")
+        N.check(N.lib().vbo_radam_step(*self._table_args(plan, scalars=True), None if state is None else state.data_ptr(),
+                                       skip), "vbo_radam_step")
 
 
 class RAdam(PlainRAdam):
@@ -459,14 +474,7 @@ class LAMB(_MultiTensorOptimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, bias_correction=True,
                  grad_averaging=True, adam_w_mode=True, use_nvlamb=False, max_grad_norm=1.0, grad_scale=1.0,
                  skip_nonfinite=False):
-        if lr < 0.0:
-            raise ValueError("Invalid learning rate: {} - should be >= 0.0".format(lr))
-        if not 0.0 <= betas[0] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[0]))
-        if not 0.0 <= betas[1] < 1.0:
-            raise ValueError("Invalid beta parameter: {} - should be in [0.0, 1.0[".format(betas[1]))
-        if not 0.0 <= eps:
-            raise ValueError("Invalid epsilon value: {} - should be >= 0.0".format(eps))
+        _check_adam_args(lr, betas, eps)
         self._init_native(max_grad_norm, grad_scale, skip_nonfinite)
         self.adam_w_mode, self.use_nvlamb = bool(adam_w_mode), bool(use_nvlamb)
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bias_correction=bool(bias_correction),
@@ -486,20 +494,10 @@ class LAMB(_MultiTensorOptimizer):
                 setattr(self, k, state[k])
 
     def _fill_hyper(self, plan, entries):
-        """(vectorised, as AdamW's; a tensor's chunks are consecutive in the chunk list, so its first chunk is the number of
-        chunks in front of it)"""
+        """(a tensor's chunks are consecutive in the chunk list, so its first chunk is the number of chunks in front of it)"""
         assert ctypes.sizeof(N.LambScalars) == _LAMB_DTYPE.itemsize
-        extra, n = plan["extra"], len(entries)
-        gi = self._group_index(plan, entries)
-        groups = self.param_groups
-        lr = np.array([g["lr"] for g in groups], dtype=np.float64)[gi]
-        b1 = np.array([g["betas"][0] for g in groups], dtype=np.float64)[gi]
-        b2 = np.array([g["betas"][1] for g in groups], dtype=np.float64)[gi]
-        eps = np.array([g["eps"] for g in groups], dtype=np.float64)[gi]
-        wd = np.array([g["weight_decay"] for g in groups], dtype=np.float64)[gi]
-        corr = np.array([bool(g["bias_correction"]) for g in groups])[gi]
-        avg = np.array([bool(g["grad_averaging"]) for g in groups])[gi]
-        steps = np.fromiter((st["step"] for _p, st, _g in entries), dtype=np.float64, count=n)
+        extra = plan["extra"]
+        lr, b1, b2, eps, wd, steps, corr, avg = self._hyper_columns(plan, entries, "bias_correction", "grad_averaging")
         extra["lr"], extra["weight_decay"], extra["beta1"], extra["beta2"], extra["eps"] = lr, wd, b1, b2, eps
         extra["beta3"] = np.where(avg, 1.0 - b1, 1.0)
         extra["one_minus_beta2"] = 1.0 - b2
@@ -517,9 +515,7 @@ class LAMB(_MultiTensorOptimizer):
         """Fixed-address buffers of the two stages, both the plan's: the per-chunk partial sums of p^2 and u^2 and the
         per-tensor trust ratios (1 until a step has run)."""
         if "trust" not in plan:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(self._NAME + ": the first step of a plan allocates its trust-ratio buffers and must run "
-                                   "eagerly before a graph capture (GraphedTrainStep's warm-up does)")
+            self._allocating("step", "trust-ratio buffers")
             device = plan["dev_tab"].device
             plan["lamb_workspace"] = torch.empty(int(N.lib().vbl_lamb_workspace(plan["n_chunks"])), dtype=torch.float32,
                                                  device=device)
@@ -528,10 +524,8 @@ class LAMB(_MultiTensorOptimizer):
 
     def _launch(self, plan, state, skip):
         workspace, trust = self._lamb_buffers(plan)
-        N.check(N.lib().vbl_lamb_step(N.stream_ptr(), plan["n_chunks"], plan["dev_tab"].data_ptr(), self._extra_ptr(plan),
-                                      plan["chunk_tensor"].data_ptr(), plan["chunk_off"].data_ptr(), CHUNK_ELEMS,
-                                      workspace.data_ptr(), trust.data_ptr(), None if state is None else state.data_ptr(),
-                                      skip), "vbl_lamb_step")
+        N.check(N.lib().vbl_lamb_step(*self._table_args(plan, scalars=True), workspace.data_ptr(), trust.data_ptr(),
+                                      None if state is None else state.data_ptr(), skip), "vbl_lamb_step")
 
     def _need_trust(self):
         if self._plan is None or "trust" not in self._plan:
