@@ -335,8 +335,9 @@ int vb_layernorm_fwd_fp8(void* stream, int64_t rows, int32_t n_cols, const float
                          const float* gamma, const float* beta, float eps, float* y, uint8_t* q, int64_t ldq,
                          float* qscale);
 
-/* dx = dy * act'(preact) elementwise (n % 4 == 0), act in {VB_ACT_GELU, VB_ACT_RELU}: the backward of
- * the GEMM epilogue activation (gelu vilbert.py:111-117, ReLU :1114,1129). */
+/* dx = dy * act'(preact) elementwise (n % 4 == 0), act in {VB_ACT_GELU, VB_ACT_RELU, VB_ACT_SWISH}: the backward of
+ * the GEMM epilogue activation (gelu vilbert.py:111-117, ReLU :1114,1129, swish :120-121 - relu' is 0 at +-0;
+ * any other act code returns VB_E_BADARG). */
 int vb_act_bwd(void* stream, int64_t n, int32_t act, const float* dy, const float* preact, float* dx);
 
 /* y = x * keep(seed, i) / (1 - p) (+ residual): nn.Dropout (vilbert.py:365,472,515,631,676,847,850,

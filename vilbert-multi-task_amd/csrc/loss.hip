@@ -15,14 +15,21 @@ namespace {
 
 constexpr int LOSS_THREADS = 256;
 
-__device__ __forceinline__ float row_lse(const float* x, int n, float* scratch) {
-    float mx = -INFINITY;
+// log-sum-exp of a row as its two parts: the row maximum mx and log(sum exp(x - mx)); lse = mx + log_s
+__device__ __forceinline__ void row_lse_parts(const float* x, int n, float* scratch, float& mx, float& log_s) {
+    mx = -INFINITY;
     for (int j = threadIdx.x; j < n; j += LOSS_THREADS) mx = fmaxf(mx, x[j]);
     mx = block_reduce<true, LOSS_THREADS>(mx, scratch);
     float s = 0.f;
     for (int j = threadIdx.x; j < n; j += LOSS_THREADS) s += expf(x[j] - mx);
     s = block_reduce<false, LOSS_THREADS>(s, scratch);
-    return mx + logf(s);
+    log_s = logf(s);
+}
+
+__device__ __forceinline__ float row_lse(const float* x, int n, float* scratch) {
+    float mx, log_s;
+    row_lse_parts(x, n, scratch, mx, log_s);
+    return mx + log_s;
 }
 
 __global__ __launch_bounds__(LOSS_THREADS) void xent_fwd_kernel(int n, const float* __restrict__ logits, long ld,
@@ -36,12 +43,16 @@ __global__ __launch_bounds__(LOSS_THREADS) void xent_fwd_kernel(int n, const flo
         return;
     }
     const float* x = logits + r * ld;
-    const float lse = row_lse(x, n, scratch);
+    float mx, log_s;
+    row_lse_parts(x, n, scratch, mx, log_s);
     if (threadIdx.x == 0) {
-        lse_out[r] = lse;
+        lse_out[r] = mx + log_s;
         // a label outside [0, n) (the reference's CrossEntropyLoss raises a device assert) poisons the loss
-        // with NaN instead of reading past the row
-        row_loss[r] = (lab >= 0 && lab < n) ? lse - x[lab] : NAN;
+        // with NaN instead of reading past the row.
+        // log_s - (x[label] - mx), not lse - x[label]: the rounded lse carries half an ulp of |lse|, so the loss of a row
+        // whose logits share a large offset lost digits (3e-5 at an offset of 1,000) that log_softmax in fp32 keeps - both
+        // terms here are of the size of the loss itself
+        row_loss[r] = (lab >= 0 && lab < n) ? log_s - (x[lab] - mx) : NAN;
     }
 }
 
