@@ -25,7 +25,12 @@ namespace vbemb {
 // vb_deterministic_fallbacks) - the caller runs the atomic kernels; > 0 = launch error (hipError_t)
 int text_embed_bwd_det(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
                        const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
-                       float* dpos, float* dtype, float* dtask);
+                       float* dpos, float* dtype, float* dtask, bool skip_pos0 = false, bool skip_type0 = false);
+// the body of vb_text_embed_bwd (embed.hip): argument checks, the ordered reduction above or the atomic kernels. skip_pos0 /
+// skip_type0 (vbb_text_embed_bwd, the baseline's padding_idx = 0 tables): position row 0 / token-type row 0 get no entry
+int text_embed_bwd(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks, const int64_t* ids,
+                   const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword, float* dpos, float* dtype,
+                   float* dtask, bool skip_pos0, bool skip_type0);
 }  // namespace vbemb
 
 namespace vbrows {

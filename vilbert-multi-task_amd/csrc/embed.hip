@@ -150,7 +150,8 @@ __global__ __launch_bounds__(256) void pos_type_grad_kernel(int batch, int n_tok
                                                             const int64_t* __restrict__ seg,
                                                             const int64_t* __restrict__ task_ids,
                                                             const float* __restrict__ dx,
-                                                            float* __restrict__ dpos, float* __restrict__ dtype) {
+                                                            float* __restrict__ dpos, float* __restrict__ dtype,
+                                                            bool skip_pos0, bool skip_type0) {
     const int n_out = n_tok + (task_ids != nullptr ? 1 : 0);
     const int t_out = blockIdx.x;
     if (task_ids != nullptr && t_out == 1) return;  // the task-token row has no position / type
@@ -171,8 +172,9 @@ __global__ __launch_bounds__(256) void pos_type_grad_kernel(int batch, int n_tok
         // the type table may hold a single row (roberta_base_6layer_6connect.json: type_vocab_size = 1)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            unsafeAtomicAdd(dpos + (long)t * hidden + col + e, ap[e]);
-            if (n_types > 0) unsafeAtomicAdd(dtype + col + e, a0[e]);
+            // (skip_*: the baseline's padding_idx = 0 rows receive nothing - vbb_text_embed_bwd)
+            if (!(skip_pos0 && t == 0)) unsafeAtomicAdd(dpos + (long)t * hidden + col + e, ap[e]);
+            if (n_types > 0 && !skip_type0) unsafeAtomicAdd(dtype + col + e, a0[e]);
             if (n_types > 1) unsafeAtomicAdd(dtype + hidden + col + e, a1[e]);
         }
     }
@@ -236,19 +238,17 @@ extern "C" int vb_additive_mask(void* stream, int64_t n, const void* mask, int32
     return 0;
 }
 
-extern "C" int vb_text_embed_bwd(void* stream, int32_t batch, int32_t n_tok, int32_t hidden, int32_t vocab,
-                                 int32_t n_types, int32_t n_tasks, const int64_t* ids, const int64_t* seg,
-                                 const int64_t* task_ids, const float* dx, float* dword, float* dpos, float* dtype,
-                                 float* dtask) {
+int vbemb::text_embed_bwd(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
+                          const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
+                          float* dpos, float* dtype, float* dtask, bool skip_pos0, bool skip_type0) {
     if (any_null({ids, seg, dx, dword, dpos, dtype}) || batch <= 0 || n_tok <= 0 || vocab <= 0 || n_types <= 0)
         return VB_E_BADARG;
     if (task_ids != nullptr && (dtask == nullptr || n_tasks <= 0)) return VB_E_BADARG;
     if (int e = check_cols(hidden)) return e;
     if (!vb_aligned16(dx)) return VB_E_ALIGN;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     // deterministic setting: the ordered keyed reduction (embed_bwd.hip); without a workspace slice, the atomics below
     const int ordered = vbemb::text_embed_bwd_det(st, batch, n_tok, hidden, vocab, n_types, n_tasks, ids, seg, task_ids,
-                                                  dx, dword, dpos, dtype, dtask);
+                                                  dx, dword, dpos, dtype, dtask, skip_pos0, skip_type0);
     if (ordered >= 0) return ordered;
     const long rows = (long)batch * (n_tok + (task_ids != nullptr ? 1 : 0));
     dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK)), block(256);
@@ -258,7 +258,15 @@ extern "C" int vb_text_embed_bwd(void* stream, int32_t batch, int32_t n_tok, int
     });
     VB_LAUNCH_CHECK();
     hipLaunchKernelGGL(pos_type_grad_kernel, dim3((unsigned)(n_tok + (task_ids != nullptr ? 1 : 0))), dim3(256), 0,
-                       st, batch, n_tok, hidden, n_types, seg, task_ids, dx, dpos, dtype);
+                       st, batch, n_tok, hidden, n_types, seg, task_ids, dx, dpos, dtype, skip_pos0, skip_type0);
     VB_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int vb_text_embed_bwd(void* stream, int32_t batch, int32_t n_tok, int32_t hidden, int32_t vocab,
+                                 int32_t n_types, int32_t n_tasks, const int64_t* ids, const int64_t* seg,
+                                 const int64_t* task_ids, const float* dx, float* dword, float* dpos, float* dtype,
+                                 float* dtask) {
+    return vbemb::text_embed_bwd(static_cast<hipStream_t>(stream), batch, n_tok, hidden, vocab, n_types, n_tasks, ids, seg,
+                                 task_ids, dx, dword, dpos, dtype, dtask, false, false);
 }

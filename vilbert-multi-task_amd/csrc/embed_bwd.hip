@@ -38,6 +38,7 @@ struct EmbKeys {
     const int64_t* ids;
     const int64_t* seg;
     const int64_t* task_ids;
+    bool skip_pos0, skip_type0;   // the baseline's padding rows (vbb_text_embed_bwd): position 0 / type 0 yield no entry
 };
 
 struct EmbTables {
@@ -60,12 +61,13 @@ __device__ __forceinline__ int entry_key(const EmbKeys& k, int e, int* row) {
         return (task >= 0 && task < k.n_tasks) ? k.key_task + (int)task : k.key_end;
     }
     const int t = (has_task && t_out >= 2) ? t_out - 1 : t_out;
-    if (slot == 1) return k.key_pos + t;
+    if (slot == 1) return (k.skip_pos0 && t == 0) ? k.key_end : k.key_pos + t;
     if (slot == 0) {
         const int64_t id = k.ids[(long)b * k.n_tok + t];
         return (id > 0 && id < k.vocab) ? (int)id : k.key_end;
     }
     const int64_t ty = k.seg[(long)b * k.n_tok + t];
+    if (k.skip_type0 && ty == 0) return k.key_end;
     return (ty >= 0 && ty < k.n_types) ? k.key_type + (int)ty : k.key_end;
 }
 
@@ -288,7 +290,8 @@ inline size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 // 0 = done, -1 = the workspace cannot hold this call (the caller runs the atomic kernels), > 0 = launch error
 int text_embed_bwd_ordered(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
                            const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx,
-                           float* dword, float* dpos, float* dtype, float* dtask, void* ws, size_t ws_bytes) {
+                           float* dword, float* dpos, float* dtype, float* dtask, void* ws, size_t ws_bytes,
+                           bool skip_pos0, bool skip_type0) {
     const int n_out = n_tok + (task_ids != nullptr ? 1 : 0);
     const long rows = (long)batch * n_out;
     const long n = 3 * rows;
@@ -323,6 +326,8 @@ int text_embed_bwd_ordered(hipStream_t st, int batch, int n_tok, int hidden, int
     k.ids = ids;
     k.seg = seg;
     k.task_ids = task_ids;
+    k.skip_pos0 = skip_pos0;
+    k.skip_type0 = skip_type0;
     EmbTables tb{dword, dpos, dtype, dtask, k.key_pos, k.key_type, k.key_task, k.key_end};
 
     const dim3 sb(256), sg((unsigned)nblk);
@@ -361,12 +366,13 @@ namespace vbemb {
 
 int text_embed_bwd_det(hipStream_t st, int batch, int n_tok, int hidden, int vocab, int n_types, int n_tasks,
                        const int64_t* ids, const int64_t* seg, const int64_t* task_ids, const float* dx, float* dword,
-                       float* dpos, float* dtype, float* dtask) {
+                       float* dpos, float* dtype, float* dtask, bool skip_pos0, bool skip_type0) {
     if (!vbdet::det_on()) return -1;
     size_t slice_bytes = 0;
     float* slice = vbdet::det_slice(st, &slice_bytes);
     const int r = slice != nullptr ? text_embed_bwd_ordered(st, batch, n_tok, hidden, vocab, n_types, n_tasks, ids, seg,
-                                                            task_ids, dx, dword, dpos, dtype, dtask, slice, slice_bytes)
+                                                            task_ids, dx, dword, dpos, dtype, dtask, slice, slice_bytes,
+                                                            skip_pos0, skip_type0)
                                    : -1;
     if (r < 0) vbdet::det_fallback();
     return r;

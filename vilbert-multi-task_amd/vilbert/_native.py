@@ -468,6 +468,19 @@ TASK_INPUT_SIGNATURES = {
     "vbd_dense_target": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _P, _P, _I64]),
 }
 
+# include/vilbert_hip_baseline.h (the single-stream baseline model, vilbert/basebert.py: joint text + image embedding, its
+# backward, the table scatter with padding rows, the pooler's tanh; prefix vbb_), mirrored one to one (checked by
+# tests/test_basebert.py)
+BASELINE_SIGNATURES = {
+    "vbb_joint_embed_fwd": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P, _F32, _P, _I32, _P, _I32, _P, _P, _P, _P, _P]),
+    "vbb_joint_embed_bwd_workspace": (_I64, [_I32, _I32, _I32, _I32]),
+    "vbb_joint_embed_bwd": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "vbb_text_embed_bwd": (ctypes.c_int, [_P, _I32, _I32, _I32, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _I32]),
+    "vbb_tanh_fwd": (ctypes.c_int, [_P, _I64, _P, _P]),
+    "vbb_tanh_bwd": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -484,7 +497,7 @@ def lib():
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
                                   + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
                                   + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())
-                                  + list(TASK_INPUT_SIGNATURES.items())):
+                                  + list(TASK_INPUT_SIGNATURES.items()) + list(BASELINE_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

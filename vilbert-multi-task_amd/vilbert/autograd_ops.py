@@ -600,6 +600,83 @@ class ImageEmbedFn(Function):
         return dsum, None, dw_loc, db_loc, dgamma, dbeta, None
 
 
+class JointEmbedFn(Function):
+    """The single-stream baseline's embedding (ops.joint_embed): one [B, T + R, H] buffer for both segments and the additive
+    mask of the two masks. Inputs: ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, typ_v (the image
+    token-type TABLE; row 1 is added to every region, basebert.py:726-728), gamma_v, beta_v, eps, mask_t, mask_v. The three
+    text tables and the image token-type table are padding_idx = 0 tables (reference basebert.py:290-298, :332-334): their
+    rows 0 get no gradient from the gather - word row 0 still gets the tied decoder's."""
+
+    @staticmethod
+    def forward(ctx, ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, typ_v, gamma_v, beta_v, eps,
+                mask_t, mask_v):
+        out, add_mask, mean, rstd, presum = ops.joint_embed(ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc,
+                                                            b_loc, typ_v[1], gamma_v, beta_v, eps, mask_t, mask_v,
+                                                            want_stats=True)
+        ctx.save_for_backward(ids, seg, loc, presum, mean, rstd, word, pos, typ, gamma_t, beta_t, w_loc, b_loc, typ_v,
+                              gamma_v, beta_v)
+        ctx.mark_non_differentiable(add_mask)
+        ctx.set_materialize_grads(False)
+        return out, add_mask
+
+    @staticmethod
+    def backward(ctx, dy, _d_mask):
+        (ids, seg, loc, presum, mean, rstd, word, pos, typ, gamma_t, beta_t, w_loc, b_loc, typ_v, gamma_v,
+         beta_v) = ctx.saved_tensors
+        if dy is None:
+            return (None,) * 17
+        need = ctx.needs_input_grad
+        ln = _Claims([gamma_t, beta_t, gamma_v, beta_v], [need[5], need[6], need[12], need[13]])
+        dx_t, dx_v, dg_t, db_t, dg_v, db_v = ops.joint_embed_bwd(dy, presum, mean, rstd, gamma_t, gamma_v, ids.shape[1],
+                                                                 *[ln.fresh_or_none(i) for i in range(4)])
+        sums = [(ln.finish_overwrite(i, v) if w else None)
+                for i, (v, w) in enumerate(zip((dg_t, db_t, dg_v, db_v), (need[5], need[6], need[12], need[13])))]
+        want = [bool(need[2]), bool(need[3]), bool(need[4]), False]
+        c = _Claims([word, pos, typ, None], want)
+        got = ops.text_embed_bwd(dx_t, ids, seg, None, tuple(word.shape), tuple(pos.shape), tuple(typ.shape), None,
+                                 out=c.views(), skip_rows0=(True, True))
+        dword, dpos, dtype = [(c.out(i, got[i]) if want[i] else None) for i in range(3)]
+        # the region rows: dx_v IS the gradient of the projected features (the feature projection's own node turns it into its
+        # weight / bias gradients); the 5-wide location projection goes through the skinny weight-gradient path, and its bias
+        # gradient colsum(dx_v) is also the gradient of row 1 of the image token-type table (row 0, the padding row, gets none)
+        want_row = bool(need[11])
+        (dw_loc,), (db_loc,) = ops.linear_bwd_weight(dx_v, loc.reshape(-1, 5), 1, w_loc.shape[0], [True])
+        cv = _Claims([w_loc, b_loc, typ_v], [bool(need[9]), bool(need[10]), want_row])
+
+        def into(i, value, row=None):
+            """`value` added into parameter i's arena slice (zero-filled, or holding an earlier contribution) - into row `row` of it
+            for the token-type table; without a slice the value itself (the table: zeros around its row)."""
+            view = cv.c[i][0]
+            if view is not None:
+                (view if row is None else view[row]).add_(value)
+                return cv.out(i, None)
+            if row is None:
+                return value
+            table = torch.zeros_like(typ_v)
+            table[row].copy_(value)
+            return table
+
+        B, S, H = presum.shape
+        return (None, None, dword, dpos, dtype, sums[0], sums[1], dx_v.view(B, S - ids.shape[1], H), None,
+                into(0, dw_loc) if need[9] else None, into(1, db_loc) if need[10] else None,
+                into(2, db_loc, row=1) if want_row else None, sums[2], sums[3], None, None, None)
+
+
+class TanhFn(Function):
+    """y = tanh(x) on the pooler's [B, H] output (vbb_tanh_fwd / vbb_tanh_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = ops.tanh(x)
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return ops.tanh_bwd(dy, y)
+
+
 class CrossEntropyFn(torch.autograd.Function):
     """nn.CrossEntropyLoss(ignore_index) (mean over counted rows) - reference vilbert.py:1453,1578-1585."""
 

@@ -205,6 +205,22 @@ def image_embed_ln(feat_proj, loc, w_loc, b_loc, gamma, beta, eps):
     return ops.image_embed_ln_fwd(feat_proj, loc, w_loc, b_loc, gamma, beta, eps)[0]
 
 
+def joint_embed_ln(ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, typ_v, gamma_v, beta_v, eps,
+                   mask_t=None, mask_v=None):
+    """The single-stream baseline's embedding -> (states [B, T + R, H], additive mask [B, T + R]): text rows word + position +
+    type under the text LayerNorm, image rows feat_proj + typ_v[1] + location projection under the image LayerNorm, and
+    (1 - mask) * -10000 of the two masks (None = all ones), in one launch."""
+    if _needs_grad(word, pos, typ, gamma_t, beta_t, feat_proj, w_loc, b_loc, typ_v, gamma_v, beta_v):
+        return A.JointEmbedFn.apply(ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, typ_v, gamma_v,
+                                    beta_v, eps, mask_t, mask_v)
+    return ops.joint_embed(ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, typ_v[1], gamma_v, beta_v,
+                           eps, mask_t, mask_v)[:2]
+
+
+def tanh(x):
+    return A.TanhFn.apply(x) if _needs_grad(x) else ops.tanh(x)
+
+
 def cross_entropy(logits, labels, ignore_index=-1):
     """nn.CrossEntropyLoss(ignore_index=...)(logits [rows, n], labels [rows]) -> 0-dim loss."""
     if _needs_grad(logits):

@@ -625,10 +625,12 @@ def text_embed_ln_fwd(ids, seg, word, pos, typ, gamma, beta, eps, task_ids=None,
     return out, mean, rstd, presum
 
 
-def text_embed_bwd(dx, ids, seg, task_ids, word_shape, pos_shape, type_shape, task_shape, out=None):
+def text_embed_bwd(dx, ids, seg, task_ids, word_shape, pos_shape, type_shape, task_shape, out=None, skip_rows0=None):
     """Scatter-add dx (gradient of the pre-LayerNorm sum) into zero tables (fresh ones, or the accumulating targets
     `out` = [dword, dpos, dtype, dtask] with None for the ones to allocate). Deterministic setting on: the ordered
-    keyed reduction of include/vilbert_hip.h on the device's workspace (registered here if no GEMM did yet)."""
+    keyed reduction of include/vilbert_hip.h on the device's workspace (registered here if no GEMM did yet).
+    skip_rows0 = (skip_pos0, skip_type0): vbb_text_embed_bwd - the baseline's padding_idx = 0 position / token-type tables,
+    whose rows 0 receive nothing (vilbert/basebert.py)."""
     dx = _contig(dx)
     ids, seg = _contig(ids), _contig(seg)
     B, T = ids.shape
@@ -643,12 +645,105 @@ def text_embed_bwd(dx, ids, seg, task_ids, word_shape, pos_shape, type_shape, ta
         dtask = out[3] if out[3] is not None else torch.zeros(task_shape, dtype=torch.float32, device=dev)
     if task_ids is not None:
         task_ids = _contig(task_ids.view(-1))
-    N.check(N.lib().vb_text_embed_bwd(
-        N.stream_ptr(), B, T, word_shape[1], word_shape[0], type_shape[0], task_shape[0] if task_shape else 0,
-        N.dev_i64(ids, "input_ids"), N.dev_i64(seg, "token_type_ids"),
-        N.dev_i64(task_ids, "task_ids"), N.dev_f32(dx, "embedding grad"), dword.data_ptr(), dpos.data_ptr(),
-        dtype.data_ptr(), dtask.data_ptr() if dtask is not None else None), "vb_text_embed_bwd")
+    args = (N.stream_ptr(), B, T, word_shape[1], word_shape[0], type_shape[0], task_shape[0] if task_shape else 0,
+            N.dev_i64(ids, "input_ids"), N.dev_i64(seg, "token_type_ids"),
+            N.dev_i64(task_ids, "task_ids"), N.dev_f32(dx, "embedding grad"), dword.data_ptr(), dpos.data_ptr(),
+            dtype.data_ptr(), dtask.data_ptr() if dtask is not None else None)
+    if skip_rows0 is None:
+        N.check(N.lib().vb_text_embed_bwd(*args), "vb_text_embed_bwd")
+    else:
+        N.check(N.lib().vbb_text_embed_bwd(*args, int(bool(skip_rows0[0])), int(bool(skip_rows0[1]))), "vbb_text_embed_bwd")
     return dword, dpos, dtype, dtask
+
+
+def _mask_arg(mask, what):
+    """(address or None, is_f32) of an attention mask for the kernels that take int64 or fp32 masks."""
+    if mask is None:
+        return None, 0
+    mask = _contig(mask)
+    if mask.dtype not in (torch.float32, torch.int64):
+        mask = mask.to(torch.int64)
+    if not mask.is_cuda:
+        raise RuntimeError("%s must live on a HIP device - no CPU fallback" % what)
+    return mask, int(mask.dtype == torch.float32)
+
+
+def joint_embed(ids, seg, word, pos, typ, gamma_t, beta_t, feat_proj, loc, w_loc, b_loc, type_row, gamma_v, beta_v, eps,
+                mask_t=None, mask_v=None, want_stats=False):
+    """The baseline's joint embedding (vbb_joint_embed_fwd): text rows and image rows of every sample in one [B, T + R, H]
+    buffer, each segment with its own LayerNorm, plus the additive mask [B, T + R] of the two masks (None = all ones).
+    Returns (out, add_mask, mean, rstd, presum); the last three are None unless want_stats."""
+    ids, seg, feat_proj, loc = _contig(ids), _contig(seg), _contig(feat_proj), _contig(loc)
+    B, T = ids.shape
+    H = word.shape[1]
+    if T > pos.shape[0]:
+        raise RuntimeError("sequence length %d exceeds max_position_embeddings %d" % (T, pos.shape[0]))
+    if feat_proj.dim() != 3 or feat_proj.shape[0] != B or feat_proj.shape[2] != H:
+        raise RuntimeError("joint_embed: the projected features must be [batch, regions, hidden]")
+    R = feat_proj.shape[1]
+    if loc.shape[-1] != 5 or loc.numel() != B * R * 5:
+        raise RuntimeError("image_loc must be [..., 5] matching the features")
+    if type_row.shape != (H,) or not type_row.is_contiguous():
+        raise RuntimeError("joint_embed: the image token-type row must be one contiguous [hidden] row")
+    dev = word.device
+    mask_t, t_f32 = _mask_arg(mask_t, "attention_mask")
+    mask_v, v_f32 = _mask_arg(mask_v, "image_attention_mask")
+    for m, n in ((mask_t, B * T), (mask_v, B * R)):
+        if m is not None and m.numel() != n:
+            raise RuntimeError("joint_embed: mask shape mismatch")
+    out = torch.empty(B, T + R, H, dtype=torch.float32, device=dev)
+    add_mask = torch.empty(B, T + R, dtype=torch.float32, device=dev)
+    mean = rstd = presum = None
+    if want_stats:
+        mean = torch.empty(B * (T + R), dtype=torch.float32, device=dev)
+        rstd = torch.empty(B * (T + R), dtype=torch.float32, device=dev)
+        presum = torch.empty_like(out)
+    N.check(N.lib().vbb_joint_embed_fwd(
+        N.stream_ptr(), B, T, R, H, word.shape[0], typ.shape[0], N.dev_i64(ids, "input_ids"), N.dev_i64(seg, "token_type_ids"),
+        N.dev_f32(word, "word_embeddings"), N.dev_f32(pos, "position_embeddings"), N.dev_f32(typ, "token_type_embeddings"),
+        N.dev_f32(gamma_t, "LayerNorm.weight"), N.dev_f32(beta_t, "LayerNorm.bias"), N.dev_f32(feat_proj, "image projection"),
+        N.dev_f32(loc, "image_loc"), N.dev_f32(w_loc, "image_location_embeddings.weight"),
+        N.dev_f32(b_loc, "image_location_embeddings.bias"), N.dev_f32(type_row, "image token_type row"),
+        N.dev_f32(gamma_v, "image LayerNorm.weight"), N.dev_f32(beta_v, "image LayerNorm.bias"), eps,
+        mask_t.data_ptr() if mask_t is not None else None, t_f32, mask_v.data_ptr() if mask_v is not None else None, v_f32,
+        out.data_ptr(), mean.data_ptr() if want_stats else None, rstd.data_ptr() if want_stats else None,
+        presum.data_ptr() if want_stats else None, add_mask.data_ptr()), "vbb_joint_embed_fwd")
+    return out, add_mask, mean, rstd, presum
+
+
+def joint_embed_bwd(dy, presum, mean, rstd, gamma_t, gamma_v, n_tok, dgamma_t=None, dbeta_t=None, dgamma_v=None, dbeta_v=None):
+    """Backward of joint_embed's two LayerNorms -> (dx_text [B * T, H], dx_img [B * R, H], dgamma_t, dbeta_t, dgamma_v,
+    dbeta_v). The four column sums: optional [H] targets, OVERWRITTEN (a deterministic two-stage sum per segment)."""
+    dy, presum = _contig(dy), _contig(presum)
+    B, S, H = presum.shape
+    T, R = n_tok, S - n_tok
+    dev = presum.device
+    dx_t = torch.empty(B * T, H, dtype=torch.float32, device=dev)
+    dx_v = torch.empty(B * R, H, dtype=torch.float32, device=dev)
+    sums = [t if t is not None else torch.empty(H, dtype=torch.float32, device=dev)
+            for t in (dgamma_t, dbeta_t, dgamma_v, dbeta_v)]
+    ws = torch.empty(N.lib().vbb_joint_embed_bwd_workspace(B, T, R, H), dtype=torch.float32, device=dev)
+    N.check(N.lib().vbb_joint_embed_bwd(
+        N.stream_ptr(), B, T, R, H, N.dev_f32(dy, "joint embedding grad_output"), N.dev_f32(presum, "joint embedding sum"),
+        N.dev_f32(mean, "joint embedding mean"), N.dev_f32(rstd, "joint embedding rstd"), N.dev_f32(gamma_t, "LayerNorm.weight"),
+        N.dev_f32(gamma_v, "image LayerNorm.weight"), dx_t.data_ptr(), dx_v.data_ptr(), sums[0].data_ptr(), sums[1].data_ptr(),
+        sums[2].data_ptr(), sums[3].data_ptr(), ws.data_ptr()), "vbb_joint_embed_bwd")
+    return (dx_t, dx_v) + tuple(sums)
+
+
+def tanh(x):
+    x = _contig(x)
+    y = torch.empty_like(x)
+    N.check(N.lib().vbb_tanh_fwd(N.stream_ptr(), x.numel(), N.dev_f32(x, "tanh input"), y.data_ptr()), "vbb_tanh_fwd")
+    return y
+
+
+def tanh_bwd(dy, y):
+    dy, y = _contig(dy), _contig(y)
+    dx = torch.empty_like(y)
+    N.check(N.lib().vbb_tanh_bwd(N.stream_ptr(), y.numel(), N.dev_f32(dy, "tanh grad_output"), N.dev_f32(y, "tanh output"),
+                                 dx.data_ptr()), "vbb_tanh_bwd")
+    return dx
 
 
 def image_embed_ln_fwd(feat_proj, loc, w_loc, b_loc, gamma, beta, eps, want_stats=False):
