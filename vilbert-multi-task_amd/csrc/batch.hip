@@ -6,6 +6,7 @@
 // once and written once into rows 1..R of [B, R+1, 2048] while its column sums become row 0.
 // HBM-bound: 8 (R + 1/2) F bytes per sample.
 #include "common.h"
+#include "batch_meta.h"
 
 namespace {
 
@@ -72,6 +73,14 @@ __global__ __launch_bounds__(256) void concap_meta_kernel(int R, int T, int obje
 
 }  // namespace
 
+int vbmeta::concap_meta(hipStream_t st, const vb_concap_batch& a) {
+    hipLaunchKernelGGL(concap_meta_kernel, dim3((unsigned)a.batch), dim3(256), 0, st, a.regions, a.tokens, a.objective,
+                       a.image_loc, a.image_mask, a.is_next, a.image_label, a.lm_label_ids, a.out_image_loc, a.out_image_mask,
+                       a.out_image_label, a.out_lm_label_ids);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int vb_concap_finish_batch(void* stream, const vb_concap_batch* a) {
     if (a == nullptr || a->batch <= 0 || a->regions <= 0 || a->tokens <= 0 || a->feat_dim <= 0) return VB_E_BADARG;
     if (a->feat_dim % 4 != 0) return VB_E_ALIGN;
@@ -85,9 +94,5 @@ extern "C" int vb_concap_finish_batch(void* stream, const vb_concap_batch* a) {
     hipLaunchKernelGGL(concap_feat_kernel, grid, dim3(256), 0, st, a->regions, a->feat_dim, a->image_feat,
                        a->masked_label, a->out_image_feat);
     VB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(concap_meta_kernel, dim3((unsigned)a->batch), dim3(256), 0, st, a->regions, a->tokens,
-                       a->objective, a->image_loc, a->image_mask, a->is_next, a->image_label, a->lm_label_ids,
-                       a->out_image_loc, a->out_image_mask, a->out_image_label, a->out_lm_label_ids);
-    VB_LAUNCH_CHECK();
-    return 0;
+    return vbmeta::concap_meta(st, *a);
 }

@@ -7,6 +7,7 @@
 // fp32 operation is an explicit round-to-nearest intrinsic: hipcc would contract a * b + c into an FMA, numpy and torch do not.
 #include "common.h"
 #include "task_rows.h"
+#include "batch_meta.h"
 #include "../../include/vilbert_hip_task_inputs.h"
 
 #pragma clang fp contract(off)
@@ -153,6 +154,12 @@ inline bool f32_extent_ok(int64_t rows, int64_t ld) {
 
 }  // namespace
 
+int vbmeta::task_meta(hipStream_t st, const vbd_task_batch& a) {
+    hipLaunchKernelGGL(task_meta_kernel, dim3((unsigned)a.batch), dim3(TM_THREADS), 0, st, a);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int vbd_task_finish_batch(void* stream, const vbd_task_batch* a) {
     if (a == nullptr || a->batch < 0 || a->total_rows < 0 || a->max_regions <= 0 || a->feat_dim <= 0) return VB_E_BADARG;
     if (!(a->iou_floor >= 0.f)) return VB_E_BADARG;          // NaN too
@@ -168,9 +175,7 @@ extern "C" int vbd_task_finish_batch(void* stream, const vbd_task_batch* a) {
     const dim3 grid((unsigned)((a->feat_dim / 4 + TF_THREADS - 1) / TF_THREADS), by, 2);
     hipLaunchKernelGGL(task_feat_kernel, grid, dim3(TF_THREADS), 0, st, *a);
     VB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(task_meta_kernel, dim3((unsigned)a->batch), dim3(TM_THREADS), 0, st, *a);
-    VB_LAUNCH_CHECK();
-    return 0;
+    return vbmeta::task_meta(st, *a);
 }
 
 extern "C" int vbd_dense_target(void* stream, int64_t rows, int32_t num_labels, int32_t K, const int32_t* labels,

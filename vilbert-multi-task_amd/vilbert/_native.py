@@ -312,6 +312,33 @@ class TaskBatchArgs(ctypes.Structure):
     ]
 
 
+class WireConcapBatch(ctypes.Structure):
+    """vbw_concap_batch (128 bytes; include/vilbert_hip_wire.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("regions", ctypes.c_int32), ("tokens", ctypes.c_int32),
+        ("feat_dim", ctypes.c_int32), ("objective", ctypes.c_int32), ("out_kind", ctypes.c_int32),
+        ("image_feat", ctypes.c_void_p), ("image_loc", ctypes.c_void_p), ("image_mask", ctypes.c_void_p),
+        ("masked_label", ctypes.c_void_p), ("is_next", ctypes.c_void_p), ("image_label", ctypes.c_void_p),
+        ("lm_label_ids", ctypes.c_void_p), ("zero_row", ctypes.c_void_p),
+        ("out_image_feat", ctypes.c_void_p), ("out_image_loc", ctypes.c_void_p), ("out_image_mask", ctypes.c_void_p),
+        ("out_image_label", ctypes.c_void_p), ("out_lm_label_ids", ctypes.c_void_p),
+    ]
+
+
+class WireTaskBatch(ctypes.Structure):
+    """vbw_task_batch (112 bytes; include/vilbert_hip_wire.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("max_regions", ctypes.c_int32), ("feat_dim", ctypes.c_int32),
+        ("out_kind", ctypes.c_int32),
+        ("iou_floor", ctypes.c_float),
+        ("total_rows", ctypes.c_int64),
+        ("feat", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("offsets", ctypes.c_void_p),
+        ("image_wh", ctypes.c_void_p), ("mean_rows", ctypes.c_void_p), ("ref_box", ctypes.c_void_p),
+        ("out_feat", ctypes.c_void_p), ("out_spatials", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
+        ("out_iou", ctypes.c_void_p),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -481,6 +508,15 @@ BASELINE_SIGNATURES = {
     "vbb_tanh_bwd": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
 }
 
+# include/vilbert_hip_wire.h (batch finishing from binary16 region features, fp32 or bf16 feature output; prefix vbw_),
+# mirrored one to one (checked by tests/test_wire16.py)
+WIRE_SIGNATURES = {
+    "vbw_concap_finish_batch": (ctypes.c_int, [_P, ctypes.POINTER(WireConcapBatch)]),
+    "vbw_task_finish_batch": (ctypes.c_int, [_P, ctypes.POINTER(WireTaskBatch)]),
+    "vbw_widen_f16": (ctypes.c_int, [_P, _I64, _P, _P]),
+}
+WIRE_OUT_KINDS = {torch.float32: 0, torch.bfloat16: 1}
+
 _lib = None
 
 
@@ -497,7 +533,8 @@ def lib():
                                   + list(TASK_SIGNATURES.items()) + list(PRETRAIN_SIGNATURES.items())
                                   + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
                                   + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())
-                                  + list(TASK_INPUT_SIGNATURES.items()) + list(BASELINE_SIGNATURES.items())):
+                                  + list(TASK_INPUT_SIGNATURES.items()) + list(BASELINE_SIGNATURES.items())
+                                  + list(WIRE_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:

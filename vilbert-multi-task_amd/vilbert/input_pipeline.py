@@ -18,6 +18,15 @@ regions a step predicts is drawn on the device by ``mask_batch`` (csrc/mask_batc
 ``vbi_zero_rows``) right before ``finish_batch``. The per-site rule and the probabilities are those of the reference's
 ``random_word`` / ``random_region``; the draws come from the library's counter-based hash, NOT from Python's ``random``
 stream, so the masks of a run differ from the reference's while having the same distribution.
+
+Half-width features (opt-in, ``DeviceBatchPipeline(..., wire_dtype=torch.float16)``): a source that keeps the detector's
+post-ReLU activations (and the region targets) as float16 sends them as they are - half the bytes per step - and the device
+widens them while it finishes the batch (csrc/wire16.hip, ``vbw_concap_finish_batch`` + ``vbw_widen_f16``;
+include/vilbert_hip_wire.h). Widening is exact, so the batch holds the bits of the default pipeline fed the widened arrays.
+``feature_dtype=torch.bfloat16`` writes the feature block as bf16 - what the bf16 stream rounds it to before its first GEMM
+anyway (``BertImageEmbeddings`` takes it as it is) - so the fp32 block and the cast launch are never made. The row clearing of
+the dynamic masking is fused into that pass (``zero_row``): there is no 16-bit row-clearing launch and the float16 buffer is
+never written.
 """
 import ctypes
 import os
@@ -36,6 +45,7 @@ RAW_UNMASKED_FIELDS = tuple("overlaps" if n == "masked_label" else n for n in RA
 _DTYPES = dict(input_ids=torch.int64, input_mask=torch.int64, segment_ids=torch.int64, lm_label_ids=torch.int64,
                is_next=torch.int64, image_feat=torch.float32, image_loc=torch.float32, image_target=torch.float32,
                image_label=torch.int64, image_mask=torch.int64, masked_label=torch.int64, overlaps=torch.float32)
+WIRE_FIELDS = ("image_feat", "image_target")      # what travels as float16 with wire_dtype=torch.float16
 _MASK64 = 0xFFFFFFFFFFFFFFFF
 BATCH_SEED_STRIDE = 0xD1B54A32D192ED03
 
@@ -106,7 +116,9 @@ def mask_batch(raw, seed, vocab_size, mask_token_id, p_select=0.15, inplace=True
     (include/vilbert_hip_inputs.h states the rule) and returns the dict `finish_batch` takes. Two native launches on the
     current stream, no torch arithmetic. inplace=True rewrites the buffers of `raw` (input_ids, lm_label_ids, image_label,
     the selected rows of image_feat); inplace=False leaves every tensor of `raw` as it is. image_target is passed through
-    untouched in both (the reference copies it before it masks)."""
+    untouched in both (the reference copies it before it masks).
+    A float16 image_feat is never rewritten, under both `inplace` settings: only the masking launch runs and its row flags
+    are returned as ``zero_row`` [batch, regions] uint8 - `finish_batch` writes those rows as zeros while it widens."""
     feat = raw["image_feat"]
     if feat.dim() != 3:
         raise RuntimeError("image_feat must be [batch, regions, feat_dim]")
@@ -123,6 +135,7 @@ def mask_batch(raw, seed, vocab_size, mask_token_id, p_select=0.15, inplace=True
             raise RuntimeError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
         return N.dev_i64(t, name)
 
+    half = feat.dtype == torch.float16
     ov = raw["overlaps"]
     if tuple(ov.shape) != (B, R, R) or not ov.is_contiguous() or not feat.is_contiguous():
         raise RuntimeError("overlaps / image_feat: expected contiguous tensors of shape %s / %s, got %s / %s"
@@ -145,29 +158,61 @@ def mask_batch(raw, seed, vocab_size, mask_token_id, p_select=0.15, inplace=True
     a.out_input_ids, a.lm_label_ids, a.image_label = out_ids.data_ptr(), lm.data_ptr(), ilab.data_ptr()
     a.masked_label, a.zero_row = masked.data_ptr(), zero_row.data_ptr()
     N.check(N.lib().vbi_concap_mask_batch(N.stream_ptr(), ctypes.byref(a)), "vbi_concap_mask_batch")
-    out_feat = feat if inplace else torch.empty_like(feat)
-    N.check(N.lib().vbi_zero_rows(N.stream_ptr(), B * R, F, N.dev_f32(feat, "image_feat"), F, zero_row.data_ptr(),
-                                  None if inplace else out_feat.data_ptr(), F), "vbi_zero_rows")
     out = {n: raw[n] for n in RAW_FIELDS if n != "masked_label"}
+    if half:
+        out_feat = feat
+        out["zero_row"] = zero_row
+    else:
+        out_feat = feat if inplace else torch.empty_like(feat)
+        N.check(N.lib().vbi_zero_rows(N.stream_ptr(), B * R, F, N.dev_f32(feat, "image_feat"), F, zero_row.data_ptr(),
+                                      None if inplace else out_feat.data_ptr(), F), "vbi_zero_rows")
     out.update(input_ids=out_ids, lm_label_ids=lm, image_label=ilab, image_feat=out_feat, masked_label=masked)
     return out
 
 
-def finish_batch(raw, objective=0):
+def widen_f16(x):
+    """Contiguous float16 DEVICE tensor -> the fp32 tensor of the same values (exact; one native launch, no torch arithmetic)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("widen_f16: expected a tensor on a HIP device - the MI355X-native path has no CPU fallback")
+    if x.dtype != torch.float16 or not x.is_contiguous():
+        raise RuntimeError("widen_f16: expected a contiguous float16 tensor, got %s" % x.dtype)
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    N.check(N.lib().vbw_widen_f16(N.stream_ptr(), x.numel(), x.data_ptr(), y.data_ptr()), "vbw_widen_f16")
+    return y
+
+
+def _out_kind(out_dtype, half, what):
+    if out_dtype not in N.WIRE_OUT_KINDS:
+        raise ValueError("%s: out_dtype must be torch.float32 or torch.bfloat16, got %r" % (what, out_dtype))
+    if out_dtype != torch.float32 and not half:
+        raise ValueError("%s: out_dtype=%s needs float16 features (fp32 features give an fp32 block)" % (what, out_dtype))
+    return N.WIRE_OUT_KINDS[out_dtype]
+
+
+def finish_batch(raw, objective=0, out_dtype=torch.float32):
     """raw: dict of DEVICE tensors named as RAW_FIELDS (worker output, unchanged). Returns the 10-tuple the
-    training loop feeds to the model. One native launch pair on the current stream; no torch arithmetic."""
+    training loop feeds to the model. One native launch pair on the current stream; no torch arithmetic.
+    A float16 image_feat is widened by the finishing pass itself (include/vilbert_hip_wire.h): the tuple holds the bits the
+    fp32 path gives on the widened features, or with out_dtype=torch.bfloat16 (float16 features only) those bits rounded to
+    bf16. With float16 features an optional raw["zero_row"] [batch, regions] uint8 (``mask_batch``) names the rows that become zeros. A float16
+    image_target is widened to fp32 (one more launch)."""
     feat = raw["image_feat"]
     if feat.dim() != 3:
         raise RuntimeError("image_feat must be [batch, regions, feat_dim]")
+    half = feat.dtype == torch.float16
+    kind = _out_kind(out_dtype, half, "finish_batch")
     B, R, F = feat.shape
     T = raw["lm_label_ids"].shape[1]
     dev = feat.device
-    out_feat = torch.empty(B, R + 1, F, dtype=torch.float32, device=dev)
+    target = raw["image_target"]
+    if isinstance(target, torch.Tensor) and target.dtype == torch.float16:
+        target = widen_f16(target)
+    out_feat = torch.empty(B, R + 1, F, dtype=out_dtype, device=dev)
     out_loc = torch.empty(B, R + 1, 5, dtype=torch.float32, device=dev)
     out_mask = torch.empty(B, R + 1, dtype=torch.int64, device=dev)
     out_ilab = torch.empty(B, R, dtype=torch.int64, device=dev)
     out_lm = torch.empty(B, T, dtype=torch.int64, device=dev)
-    a = N.ConcapBatch()
+    a = N.WireConcapBatch() if half else N.ConcapBatch()
     a.batch, a.regions, a.tokens, a.feat_dim, a.objective = B, R, T, F, int(objective)
 
     def f32(name, shape):
@@ -182,15 +227,29 @@ def finish_batch(raw, objective=0):
             raise RuntimeError("%s: expected shape %s, got %s" % (name, shape, tuple(t.shape)))
         return N.dev_i64(t, name)
 
-    a.image_feat, a.image_loc = f32("image_feat", (B, R, F)), f32("image_loc", (B, R, 5))
+    if half:
+        if not feat.is_cuda or tuple(feat.shape) != (B, R, F) or not feat.is_contiguous():
+            raise RuntimeError("image_feat: expected a contiguous float16 tensor on a HIP device")
+        a.image_feat, a.out_kind = feat.data_ptr(), kind
+        flags = raw.get("zero_row")
+        if flags is not None:
+            if not flags.is_cuda or flags.dtype != torch.uint8 or tuple(flags.shape) != (B, R) or not flags.is_contiguous():
+                raise RuntimeError("zero_row: expected a contiguous uint8 tensor of shape %s on a HIP device" % ((B, R),))
+            a.zero_row = flags.data_ptr()
+    else:
+        a.image_feat = f32("image_feat", (B, R, F))
+    a.image_loc = f32("image_loc", (B, R, 5))
     a.image_mask, a.masked_label = i64("image_mask", (B, R)), i64("masked_label", (B, R))
     a.is_next, a.image_label = i64("is_next", (B,)), i64("image_label", (B, R))
     a.lm_label_ids = i64("lm_label_ids", (B, T))
     a.out_image_feat, a.out_image_loc = out_feat.data_ptr(), out_loc.data_ptr()
     a.out_image_mask, a.out_image_label, a.out_lm_label_ids = out_mask.data_ptr(), out_ilab.data_ptr(), out_lm.data_ptr()
-    N.check(N.lib().vb_concap_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vb_concap_finish_batch")
+    if half:
+        N.check(N.lib().vbw_concap_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vbw_concap_finish_batch")
+    else:
+        N.check(N.lib().vb_concap_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vb_concap_finish_batch")
     return (raw["input_ids"], raw["input_mask"], raw["segment_ids"], out_lm, raw["is_next"], out_feat, out_loc,
-            raw["image_target"], out_ilab, out_mask)
+            target, out_ilab, out_mask)
 
 
 class _Slot(object):
@@ -226,25 +285,50 @@ class DeviceBatchPipeline(object):
     masking=None: the source masks (the reference's workers), as above. masking=Masking(...): the source yields UNMASKED
     batches in RAW_UNMASKED_FIELDS order (``unmasked_preprocess`` makes such a worker class) and every batch is masked on the
     compute stream by ``mask_batch`` with ``masking.next_seed()`` before it is finished: the Masking object counts the batches
-    across iterations (and across pipelines that share it), so each pass over a source draws new masks."""
+    across iterations (and across pipelines that share it), so each pass over a source draws new masks.
 
-    def __init__(self, source, device, objective=0, depth=2, staging=None, masking=None):
+    wire_dtype=None: image_feat and image_target cross the bus as fp32 (a float16 array is widened on the host first).
+    wire_dtype=torch.float16: the source supplies float16 arrays for both (anything else raises ValueError - the pipeline
+    never narrows), the slot buffers are float16 and the device widens them; the yielded batch holds the bits of the default
+    pipeline fed the widened arrays. feature_dtype=torch.bfloat16 (with the float16 wire only) yields image_feat rounded to
+    bf16, for the bf16 stream."""
+
+    def __init__(self, source, device, objective=0, depth=2, staging=None, masking=None, wire_dtype=None,
+                 feature_dtype=torch.float32):
         self.source, self.device, self.objective = source, torch.device(device), int(objective)
         self.masking = masking
+        if wire_dtype not in (None, torch.float16):
+            raise ValueError("wire_dtype must be None or torch.float16, got %r" % (wire_dtype,))
+        _out_kind(feature_dtype, wire_dtype is not None, "DeviceBatchPipeline")
+        self.wire_dtype, self.feature_dtype = wire_dtype, feature_dtype
         self.fields = RAW_FIELDS if masking is None else RAW_UNMASKED_FIELDS
-        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self._copy_stream = None
         self.slots = [_Slot() for _ in range(max(2, depth))]
         # "pinned": numpy -> pinned host buffer -> asynchronous DMA.  "direct": hand the pageable numpy memory to
         # the runtime's own copy path (it stages through its internal pinned chunks; blocks the host for the
         # duration of the transfer but never makes the CPU write through an uncached host mapping).
         self.staging = staging or os.environ.get("VB_PIPE_STAGING", "direct")   # measured: 131 vs 137-154 ms / step
 
+    @property
+    def copy_stream(self):
+        if self._copy_stream is None:                       # made on first use: the constructor touches no device
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        return self._copy_stream
+
+    def _dtype(self, name):
+        return self.wire_dtype if self.wire_dtype is not None and name in WIRE_FIELDS else _DTYPES[name]
+
     def _stage(self, slot, batch):
+        fields = dict(zip(self.fields, batch[:len(self.fields)]))
+        if self.wire_dtype is not None:
+            for name in WIRE_FIELDS:
+                if np.asarray(fields[name]).dtype != np.float16:
+                    raise ValueError("%s: wire_dtype=torch.float16 takes float16 arrays from the source, got %s (the pipeline "
+                                     "never narrows)" % (name, np.asarray(fields[name]).dtype))
         if slot.copied is not None:
             slot.copied.synchronize()                       # pinned buffers free again (long done)
         if slot.released is not None:
             self.copy_stream.wait_event(slot.released)      # device buffers free once that step has run
-        fields = dict(zip(self.fields, batch[:len(self.fields)]))
         slot.extra = tuple(batch[len(self.fields):])
         with torch.cuda.stream(self.copy_stream):
             for name in self.fields:
@@ -253,7 +337,7 @@ class DeviceBatchPipeline(object):
                     slot.ensure(name, np.shape(fields[name]), _DTYPES[name], self.device)
                     continue
                 arr = np.ascontiguousarray(fields[name])
-                h, d = slot.ensure(name, arr.shape, _DTYPES[name], self.device)
+                h, d = slot.ensure(name, arr.shape, self._dtype(name), self.device)
                 if self.staging == "direct" and arr.dtype == h.numpy().dtype:
                     d.copy_(torch.from_numpy(arr), non_blocking=False)
                 else:
@@ -278,7 +362,7 @@ class DeviceBatchPipeline(object):
             raw, m = slot.dev, self.masking
             if m is not None:
                 raw = mask_batch(raw, m.next_seed(), m.vocab_size, m.mask_token_id, m.p_select, inplace=True)
-            out = finish_batch(raw, self.objective)
+            out = finish_batch(raw, self.objective, self.feature_dtype)
             yield out + slot.extra
             slot.released = torch.cuda.Event()
             slot.released.record(torch.cuda.current_stream(self.device))   # after the caller's step

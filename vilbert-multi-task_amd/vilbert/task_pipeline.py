@@ -11,6 +11,11 @@ concatenation only), pixel boxes, image sizes, sparse answers or a reference box
 (csrc/task_batch.hip, ``vbd_task_finish_batch`` + ``vbd_dense_target``; include/vilbert_hip_task_inputs.h states the arithmetic,
 held bit for bit to the reference's own). ``TaskBatchPipeline`` yields the tuple the reference's datasets collate to:
     (features, spatials, image_mask, question, target, input_mask, segment_ids, co_attention_mask, question_id)
+
+Half-width features (opt-in): ``pack_task_samples(..., dtype=np.float16)`` packs float16 region features,
+``TaskBatchPipeline(..., wire_dtype=torch.float16)`` sends them as they are and the device widens them while it builds the batch
+(csrc/wire16.hip, ``vbw_task_finish_batch``; include/vilbert_hip_wire.h) - the bits of the default builder on the widened
+arrays, or with ``feature_dtype=torch.bfloat16`` those bits rounded to bf16 for the bf16 stream.
 """
 import ctypes
 import os
@@ -19,7 +24,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .input_pipeline import _Slot
+from .input_pipeline import _Slot, _out_kind
 
 PACKED_FIELDS = ("feat", "boxes", "offsets", "image_wh", "mean_rows")
 TOKEN_FIELDS = ("question", "input_mask", "segment_ids")
@@ -36,14 +41,24 @@ def raw_item(item):
                 image_w=int(item["image_w"]), image_h=int(item["image_h"]))
 
 
-def pack_task_samples(samples, mean_rows=None):
+def pack_task_samples(samples, mean_rows=None, dtype=np.float32):
     """samples: raw samples (``raw_item``), one per IMAGE - a multi-image task (NLVR2 pairs, retrieval options) packs each
     image as its own entry. Returns numpy arrays: feat [N, F] and boxes [N, 4] (the samples back to back), offsets [B + 1]
     int64, image_wh [B, 2] int32, mean_rows [B] int32 (the leading rows of a sample that enter its mean; default: all of them -
-    the refer-expression training split appends ground-truth rows that do not). Host-side concatenation only."""
+    the refer-expression training split appends ground-truth rows that do not). Host-side concatenation only.
+    dtype=np.float16: for a store that keeps float16 features - every sample's features must BE float16 (ValueError
+    otherwise: nothing is narrowed here) and feat is packed as float16, for ``wire_dtype=torch.float16``."""
     if len(samples) == 0:
         raise ValueError("no samples to pack")
-    feats = [np.asarray(s["feat"], dtype=np.float32) for s in samples]
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float16)):
+        raise ValueError("dtype must be numpy.float32 or numpy.float16, got %r" % (dtype,))
+    if dtype == np.float16:
+        for i, s in enumerate(samples):
+            if np.asarray(s["feat"]).dtype != np.float16:
+                raise ValueError("sample %d: dtype=float16 takes float16 features, got %s (the packer never narrows)"
+                                 % (i, np.asarray(s["feat"]).dtype))
+    feats = [np.asarray(s["feat"], dtype=dtype) for s in samples]
     boxes = [np.asarray(s["boxes"], dtype=np.float32).reshape(-1, 4) for s in samples]
     F = feats[0].shape[-1]
     for i, (f, bx) in enumerate(zip(feats, boxes)):
@@ -77,25 +92,31 @@ def _dev(t, name, dtype, shape):
     return t.data_ptr()
 
 
-def finish_task_batch(packed_dev, max_regions, ref_box=None, iou_floor=0.0):
+def finish_task_batch(packed_dev, max_regions, ref_box=None, iou_floor=0.0, out_dtype=torch.float32):
     """packed_dev: dict of DEVICE tensors named as ``pack_task_samples`` names them (mean_rows may be missing or None: all
     rows enter the mean). Returns (features [B, R, F], spatials [B, R, 5], image_mask [B, R] int64) and, with ref_box [B, 4]
     (pixel x1, y1, x2, y2), the region-IoU target [B, R, 1] (values below iou_floor become 0). One native launch pair on the
-    current stream; every element of the outputs is written by it, no torch arithmetic."""
+    current stream; every element of the outputs is written by it, no torch arithmetic.
+    A float16 feat is widened by the same pass: the bits the fp32 builder gives on the widened rows, or with
+    out_dtype=torch.bfloat16 (float16 feat only) those bits rounded to bf16."""
     feat, offsets = packed_dev["feat"], packed_dev["offsets"]
     if not isinstance(feat, torch.Tensor) or feat.dim() != 2 or not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 \
             or offsets.shape[0] < 1:
         raise RuntimeError("feat must be [rows, feat_dim] and offsets [batch + 1]")
     (n, F), B, R, dev = feat.shape, offsets.shape[0] - 1, int(max_regions), feat.device
-    a = N.TaskBatchArgs()
+    half = feat.dtype == torch.float16
+    kind = _out_kind(out_dtype, half, "finish_task_batch")
+    a = N.WireTaskBatch() if half else N.TaskBatchArgs()
     a.batch, a.max_regions, a.feat_dim, a.iou_floor, a.total_rows = B, R, F, float(iou_floor), n
-    a.feat = _dev(feat, "feat", torch.float32, (n, F))
+    if half:
+        a.out_kind = kind
+    a.feat = _dev(feat, "feat", torch.float16 if half else torch.float32, (n, F))
     a.boxes = _dev(packed_dev["boxes"], "boxes", torch.float32, (n, 4))
     a.offsets = _dev(offsets, "offsets", torch.int64, (B + 1,))
     a.image_wh = _dev(packed_dev["image_wh"], "image_wh", torch.int32, (B, 2))
     if packed_dev.get("mean_rows") is not None:
         a.mean_rows = _dev(packed_dev["mean_rows"], "mean_rows", torch.int32, (B,))
-    out_feat = torch.empty(B, max(R, 0), F, dtype=torch.float32, device=dev)
+    out_feat = torch.empty(B, max(R, 0), F, dtype=out_dtype, device=dev)
     out_sp = torch.empty(B, max(R, 0), 5, dtype=torch.float32, device=dev)
     out_mask = torch.empty(B, max(R, 0), dtype=torch.int64, device=dev)
     a.out_feat, a.out_spatials, a.out_mask = out_feat.data_ptr(), out_sp.data_ptr(), out_mask.data_ptr()
@@ -105,7 +126,10 @@ def finish_task_batch(packed_dev, max_regions, ref_box=None, iou_floor=0.0):
         out_iou = torch.empty(B, max(R, 0), 1, dtype=torch.float32, device=dev)
         a.out_iou = out_iou.data_ptr()
         out += (out_iou,)
-    N.check(N.lib().vbd_task_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vbd_task_finish_batch")
+    if half:
+        N.check(N.lib().vbw_task_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vbw_task_finish_batch")
+    else:
+        N.check(N.lib().vbd_task_finish_batch(N.stream_ptr(), ctypes.byref(a)), "vbd_task_finish_batch")
     return out
 
 
@@ -137,19 +161,35 @@ class TaskBatchPipeline(object):
     modes of ``DeviceBatchPipeline``). The packed arrays change length from batch to batch: a slot's buffers are sized by
     CAPACITY (first dimension, grow only) and a batch uses a leading view of them. The token tensors are copied as they are
     and alias the slot's device buffers: they stay valid until the caller asks for batch i + depth - 1. co_attention_mask
-    is one cached zero tensor [B, R, T] (the reference builds a fresh one per sample; nothing writes to it)."""
+    is one cached zero tensor [B, R, T] (the reference builds a fresh one per sample; nothing writes to it).
 
-    def __init__(self, source, device, max_regions, target=None, depth=2, staging=None):
+    wire_dtype=torch.float16: ``feat`` must be a float16 array (``pack_task_samples(..., dtype=np.float16)``; anything else
+    raises ValueError - the pipeline never narrows), crosses the bus as it is and is widened on the device: the bits of the
+    default pipeline fed the widened array. feature_dtype=torch.bfloat16 (with the float16 wire only) yields the features
+    rounded to bf16."""
+
+    def __init__(self, source, device, max_regions, target=None, depth=2, staging=None, wire_dtype=None,
+                 feature_dtype=torch.float32):
         self.source, self.device, self.max_regions = source, torch.device(device), int(max_regions)
+        if wire_dtype not in (None, torch.float16):
+            raise ValueError("wire_dtype must be None or torch.float16, got %r" % (wire_dtype,))
+        _out_kind(feature_dtype, wire_dtype is not None, "TaskBatchPipeline")
+        self.wire_dtype, self.feature_dtype = wire_dtype, feature_dtype
         if target is not None and (len(target) != 2 or target[0] not in ("dense", "iou")):
             raise ValueError("target must be None, ('dense', num_labels) or ('iou', floor), got %r" % (target,))
         self.target = target
         extra = {None: ("target",), "dense": ("labels", "scores"), "iou": ("ref_box",)}[target[0] if target else None]
         self.fields = PACKED_FIELDS + TOKEN_FIELDS + ("question_id",) + extra
-        self.copy_stream = torch.cuda.Stream(device=self.device)
+        self._copy_stream = None
         self.slots = [_Slot() for _ in range(max(2, depth))]
         self.staging = staging or os.environ.get("VB_PIPE_STAGING", "direct")
         self._co_attention = {}
+
+    @property
+    def copy_stream(self):
+        if self._copy_stream is None:                       # made on first use: the constructor touches no device
+            self._copy_stream = torch.cuda.Stream(device=self.device)
+        return self._copy_stream
 
     def _ensure(self, slot, name, shape, dtype):
         """Leading views [shape[0]] of the slot's host / device buffers of `name`, reallocated only when the batch does not
@@ -164,6 +204,9 @@ class TaskBatchPipeline(object):
         return (None if h is None else h[:shape[0]]), d[:shape[0]]
 
     def _stage(self, slot, batch):
+        if self.wire_dtype is not None and np.asarray(batch["feat"]).dtype != np.float16:
+            raise ValueError("feat: wire_dtype=torch.float16 takes a float16 array from the source, got %s (the pipeline never "
+                             "narrows)" % np.asarray(batch["feat"]).dtype)
         if slot.copied is not None:
             slot.copied.synchronize()                       # pinned buffers free again (long done)
         if slot.released is not None:
@@ -174,7 +217,8 @@ class TaskBatchPipeline(object):
                 arr = np.ascontiguousarray(batch[name])
                 src = torch.from_numpy(arr)
                 # a target the source supplies keeps its own dtype (int64 labels for cross-entropy, fp32 soft labels)
-                h, d = self._ensure(slot, name, arr.shape, _DTYPES.get(name, src.dtype))
+                dtype = self.wire_dtype if name == "feat" and self.wire_dtype is not None else _DTYPES.get(name, src.dtype)
+                h, d = self._ensure(slot, name, arr.shape, dtype)
                 if h is None:
                     d.copy_(src, non_blocking=False)        # "direct": dtype conversion, if any, is the runtime's
                 else:
@@ -207,7 +251,7 @@ class TaskBatchPipeline(object):
             v = slot.extra
             kind = self.target[0] if self.target else None
             out = finish_task_batch(v, self.max_regions, ref_box=v["ref_box"] if kind == "iou" else None,
-                                    iou_floor=float(self.target[1]) if kind == "iou" else 0.0)
+                                    iou_floor=float(self.target[1]) if kind == "iou" else 0.0, out_dtype=self.feature_dtype)
             if kind == "dense":
                 target = dense_target(v["labels"], v["scores"], int(self.target[1]))
             else:

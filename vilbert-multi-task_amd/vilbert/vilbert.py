@@ -973,8 +973,10 @@ class BertImageEmbeddings(nn.Module):
     def forward(self, input_ids, input_loc):
         if _native.bf16_stream() and input_ids.is_cuda:
             # bf16 mode: the [regions x 2048] features are rounded to bf16 once (they need no gradient), the projection
-            # runs on the bf16 GEMM with an fp32 result for the (fp32) location + sum + LayerNorm row kernel
-            proj = F.linear_f32_out(F.to_bf16(input_ids.float()), self.image_embeddings.weight, self.image_embeddings.bias)
+            # runs on the bf16 GEMM with an fp32 result for the (fp32) location + sum + LayerNorm row kernel. A block that
+            # arrives as bf16 (the input pipelines' feature_dtype=torch.bfloat16) is that rounded block: no copy, no cast
+            x16 = input_ids if input_ids.dtype == torch.bfloat16 else F.to_bf16(input_ids.float())
+            proj = F.linear_f32_out(x16, self.image_embeddings.weight, self.image_embeddings.bias)
         else:
             proj = F.linear(input_ids.float(), self.image_embeddings.weight, self.image_embeddings.bias)
         out = F.image_embed_ln(proj, input_loc.float(), self.image_location_embeddings.weight,
