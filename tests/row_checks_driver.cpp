@@ -23,7 +23,18 @@ int main() {
     show("extent_2_half_plus_1", vb_extent_ok(2, big / 2 + 1));
     show("extent_max_2", vb_extent_ok(big, 2));
 
-    const int64_t widths[] = {0, 1, 256, 257, 30522, 1601};
+    // byte offsets of rows * ld elements (the batch-finishing calls): 2-byte binary16 rows, 4-byte fp32 rows
+    const int64_t p50 = (int64_t)1 << 50, p52 = (int64_t)1 << 52;
+    show("bytes_0_max_4", vb_byte_extent_ok(0, big, 4));
+    show("bytes_neg_max_4", vb_byte_extent_ok(-1, big, 4));
+    show("bytes_p50_2048_2", vb_byte_extent_ok(p50, 2048, 2));          // 2^62 bytes
+    show("bytes_p50_2048_4", vb_byte_extent_ok(p50, 2048, 4));          // 2^63 bytes
+    show("bytes_p52_2048_2", vb_byte_extent_ok(p52, 2048, 2));          // 2^63 elements: the product itself overflows
+    show("bytes_1_quarter_4", vb_byte_extent_ok(1, big / 4, 4));
+    show("bytes_1_quarter_plus_1_4", vb_byte_extent_ok(1, big / 4 + 1, 4));
+    show("bytes_max_2_2", vb_byte_extent_ok(big, 2, 2));
+
+    const int64_t widths[] ={0, 1, 256, 257, 30522, 1601};
     for (int64_t n : widths) {
         char name[32];
         snprintf(name, sizeof name, "padded_%lld", (long long)n);

@@ -1,4 +1,4 @@
-"""The host-side argument checks and launch arithmetic of the row kernels (csrc/row_checks.h: vb_extent_ok, vb_padded256,
+"""The host-side argument checks and launch arithmetic of the row kernels (csrc/row_checks.h: vb_extent_ok, vb_byte_extent_ok, vb_padded256,
 vb_grid_for, vb_row16_ok / vb_row32_ok - what every vbh_ / vbf_ / vbt_ / vbp_ entry point tests before it launches) at their
 boundaries, through the stand-alone tests/row_checks_driver.cpp - built with the host compiler's address and
 undefined-behaviour sanitizers where it has them (the int64 products of vb_extent_ok and vb_grid_for must not overflow)."""
@@ -31,6 +31,14 @@ def cases(tmp_path_factory):
 def test_extent_fits_int64(cases):
     got = {k[len("extent_"):]: v for k, v in cases.items() if k.startswith("extent_")}
     assert got == {"0_max": 1, "neg_max": 1, "1_max": 1, "2_half": 1, "2_half_plus_1": 0, "max_2": 0}
+
+
+def test_byte_extent_fits_int64(cases):
+    """vb_byte_extent_ok(rows, ld, bytes per element): the one check of the batch-finishing calls (batch.hip, task_batch.hip,
+    mask_batch.hip) - the element count and its byte offset both stay inside int64, and neither product overflows on the way."""
+    got = {k[len("bytes_"):]: v for k, v in cases.items() if k.startswith("bytes_")}
+    assert got == {"0_max_4": 1, "neg_max_4": 1, "p50_2048_2": 1, "p50_2048_4": 0, "p52_2048_2": 0, "1_quarter_4": 1,
+                   "1_quarter_plus_1_4": 0, "max_2_2": 0}
 
 
 def test_padded_width(cases):

@@ -1,4 +1,4 @@
-"""Host side of the half-width (float16) feature wire (csrc/wire16.hip; include/vilbert_hip_wire.h; vilbert.input_pipeline and
+"""Host side of the half-width (float16) feature wire (csrc/batch.hip, task_batch.hip, wire16.hip; include/vilbert_hip_wire.h; vilbert.input_pipeline and
 vilbert.task_pipeline with wire_dtype=torch.float16): the header, its ctypes mirror and the built library agree, argument errors
 come back before any launch, the Python layer refuses to narrow fp32 arrays, and the masking case that
 tests/test_wire16_gpu.py runs for the fused row clearing is not an empty one. No compute is launched."""
@@ -65,7 +65,9 @@ def test_header_declares_the_wire_entry_points_and_names_no_other_headers_entry_
     assert not re.search(r"\bvb_[a-z]", own)                      # the other headers are referred to by file name only
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert re.search(r"^SRCS = .*\bwire16\.hip\b", make, flags=re.M)
-    assert re.search(r"^HDRS = .*\bbatch_meta\.h\b.*vilbert_hip_wire\.h\b", make, flags=re.M)
+    assert re.search(r"^HDRS = .*\bfeat_rows\.h\b.*vilbert_hip_wire\.h\b", make, flags=re.M)
+    gone = "batch_" + "meta"                                      # the header the entry points used to share launches through
+    assert gone not in make and not os.path.exists(os.path.join(CSRC, gone + ".h"))
 
 
 def test_ctypes_mirror_and_library_agree_with_the_header(native):
@@ -106,11 +108,20 @@ def test_argument_structs_match_their_mirrors_field_for_field(native, struct):
 
 
 def test_resource_file_of_the_new_source_shows_no_scratch(native):
-    text = open(os.path.join(os.path.dirname(native.LIB_PATH), "wire16.resource.txt")).read()
-    found = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", text, flags=re.S)
-    names = " ".join(fn for fn, _ in found)
-    assert len(found) == 5 and all(k in names for k in ("concap_feat16_kernel", "task_feat16_kernel", "widen_f16_kernel"))
-    assert all(int(scratch) == 0 for _, scratch in found), found
+    """Every feature kernel by its mangled name, in the resource file of the source that launches it: the instantiations of
+    csrc/feat_rows.h - In = f (fp32) or DF16_ (binary16), Out = f or the bf16 element - batch.hip's own fp32 kernel (no
+    template arguments: ...kernelE) and the flat widening kernel. Each is there exactly once and none spills."""
+    scratch = {}
+    for src in ("batch", "task_batch", "wire16"):
+        text = open(os.path.join(os.path.dirname(native.LIB_PATH), src + ".resource.txt")).read()
+        found = re.findall(r"Function Name: (\S+).*?ScratchSize \[bytes/lane\]: (\d+)", text, flags=re.S)
+        scratch[src] = [(fn, int(s)) for fn, s in found if "feat_kernel" in fn or "widen" in fn]
+    for src, kernel, kinds in (("batch", "concap_feat_kernel", ("Eii", "IDF16_f", "IDF16_NS_4bf16E")),
+                               ("task_batch", "task_feat_kernel", ("Iff", "IDF16_f", "IDF16_NS_4bf16E"))):
+        assert len(scratch[src]) == 3, scratch[src]
+        for kind in kinds:
+            assert [s for fn, s in scratch[src] if kernel + kind in fn] == [0], (kernel, kind, scratch[src])
+    assert len(scratch["wire16"]) == 1 and "widen_f16_kernel" in scratch["wire16"][0][0] and scratch["wire16"][0][1] == 0
 
 
 # ---- argument errors -------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
-"""The half-width (float16) feature wire on the GPU (csrc/wire16.hip; vilbert.input_pipeline / vilbert.task_pipeline with float16
-features; BertImageEmbeddings with a bf16 feature block). The yardstick is always the EXISTING fp32 path run on the exactly
-widened arrays - never the code under test - and every comparison is torch.equal: widening binary16 is exact, the sums run in the
-same order, the bf16 output is one correctly rounded conversion of the fp32 result. There is no tolerance anywhere in this file."""
+"""The half-width (float16) feature wire on the GPU (csrc/feat_rows.h, batch.hip, task_batch.hip, wire16.hip; vilbert.input_pipeline
+/ vilbert.task_pipeline with float16 features; BertImageEmbeddings with a bf16 feature block). The yardstick is the fp32 path run
+on the exactly widened arrays and - most of the two being instantiations of one kernel template - the numpy restatements of
+both calls (section 4b); every comparison is torch.equal: widening binary16 is exact, the sums run in the same order, the bf16
+output is one correctly rounded conversion of the fp32 result. There is no tolerance anywhere in this file."""
 import ctypes
 
 import numpy as np
@@ -222,6 +223,89 @@ def test_task_builder_small_width_partial_means_and_an_empty_sample(floor):
     _check_task(half, wide, 6)
     half["mean_rows"] = wide["mean_rows"] = None
     _check_task(half, wide, 12)                                                # zero rows behind every sample
+
+
+# ---- 4b: host yardsticks -------------------------------------------------------------------------------------------------------
+# The float16 kernels and the fp32 task builder are instantiations of ONE kernel template (csrc/feat_rows.h), so the comparisons
+# above partly hold one instantiation to another. These hold every feature kernel to a numpy restatement that shares no code
+# with the library (the fp32 task builder: tests/test_task_batch_gpu.py).
+_ORACLE = {}
+
+
+def _concap_oracle(F, R, half):
+    """(raw dict as the call takes it, {objective: oracle output}) for B = 3, T = 6; sample 0 has no masked_label == 0 (the
+    count falls back to 1). half: float16 features with full mantissas, the oracle runs on their exact widening."""
+    key = (F, R, half)
+    if key not in _ORACLE:
+        raw = bo.make_raw_batch(3, tokens=6, regions=R, feat_dim=F, n_classes=9, vocab=99, seed=F + R)
+        assert (raw["masked_label"][0] != 0).all() and (raw["masked_label"][1:] == 0).any()
+        wide = raw
+        if half:
+            raw = dict(raw, image_feat=wc.f16_values((3, R, F), F + R))
+            wide = dict(raw, image_feat=wc.widen(raw["image_feat"]))
+        _ORACLE[key] = (raw, {obj: bo.finish_batch(wide, obj) for obj in (0, 1)})
+    return _ORACLE[key]
+
+
+def _equals_oracle(got, want, bf16=False):
+    assert len(got) == len(bo.OUT_FIELDS)
+    for g, name in zip(got, bo.OUT_FIELDS):
+        w = torch.from_numpy(np.ascontiguousarray(want[name]))
+        if bf16 and name == "image_feat":
+            w = w.to(torch.bfloat16)                       # torch's CPU cast: round to nearest even
+        _same(g.cpu(), w, name)
+
+
+@pytest.mark.parametrize("objective", [0, 1])
+@pytest.mark.parametrize("R", [3, 5])
+@pytest.mark.parametrize("F", [4, 260, 1028])
+def test_fp32_concap_finishing_equals_the_host_oracle(F, R, objective):
+    """F = 4: one column group; 260: one partial block of 256 threads; 1028: a second block that holds a single group.
+    R = 3: fewer rows than the loop's unroll of 4; 5: one unrolled pass and a remainder."""
+    from vilbert import input_pipeline as ip
+    raw, want = _concap_oracle(F, R, False)
+    _equals_oracle(ip.finish_batch(_to_dev(raw), objective), want[objective])
+
+
+@pytest.mark.parametrize("objective", [0, 1])
+@pytest.mark.parametrize("R", [5, 9])
+@pytest.mark.parametrize("F", [8, 264])
+def test_float16_concap_finishing_equals_the_host_oracle_on_the_widened_features(F, R, objective):
+    """R = 9 crosses the 8 rows in flight by one; both output kinds."""
+    from vilbert import input_pipeline as ip
+    raw, want = _concap_oracle(F, R, True)
+    dev = _to_dev(raw)
+    _equals_oracle(ip.finish_batch(dev, objective), want[objective])
+    _equals_oracle(ip.finish_batch(dev, objective, out_dtype=torch.bfloat16), want[objective], bf16=True)
+
+
+def test_float16_concap_finishing_with_row_flags_equals_the_host_oracle_on_the_cleared_features():
+    from vilbert import input_pipeline as ip
+    c = wc.MASK_CASE
+    raw, feat = wc.mask_case_raw()
+    masked = mr.mask_batch(raw, c["seed"], wc.VOCAB, wc.MASK_ID, c["p"])        # host: the flagged fp32 rows are zeros
+    want = bo.finish_batch(masked, 0)
+    dev = _to_dev(dict(masked, image_feat=feat, zero_row=wc.mask_case_flags(raw)))
+    _equals_oracle(ip.finish_batch(dev, 0), want)
+    _equals_oracle(ip.finish_batch(dev, 0, out_dtype=torch.bfloat16), want, bf16=True)
+
+
+@pytest.mark.parametrize("F", [8, 264])
+def test_float16_task_builder_equals_the_host_restatement_on_the_widened_rows(F):
+    """max_regions = 6; samples of 0, 1, 5, 9 and 12 rows: empty, a mean only, a fit, more than the 8 rows in flight, one
+    that is truncated; the sample of 5 rows takes its mean over 3. Both output kinds."""
+    from vilbert import task_pipeline as tp
+    packed = tr.make_packed([0, 1, 5, 9, 12], F, seed=F, mean_rows=[0, 1, 3, 9, 12])
+    half, wide = _narrow_packed(packed, F + 1)
+    want = tr.finish_task_batch(wide, 6)
+    assert want[2].sum(1).tolist() == [1, 2, 6, 6, 6] and not want[0][0].any()
+    dev = _to_dev(half)
+    for out_dtype in (torch.float32, torch.bfloat16):
+        got = tp.finish_task_batch(dev, 6, out_dtype=out_dtype)
+        assert len(got) == 3
+        _same(got[0].cpu(), torch.from_numpy(want[0]).to(out_dtype), "features, %s" % out_dtype)
+        _same(got[1].cpu(), torch.from_numpy(want[1]), "spatials")
+        _same(got[2].cpu(), torch.from_numpy(want[2]), "image_mask")
 
 
 # ---- 5: the flat widening ------------------------------------------------------------------------------------------------------

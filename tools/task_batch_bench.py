@@ -12,8 +12,9 @@ image, 10 sparse answers, 3,129 labels):
   kernels                  device events around back-to-back launches through the C ABI into preallocated outputs:
                              task inputs  vbd_task_finish_batch (the feature kernel plus the small box / mask kernel); the GB/s
                                           figure charges ALL of that time to the feature kernel's 4 F (N + B R) bytes
-                             concap       vb_concap_finish_batch (csrc/batch.hip, concap_feat_kernel plus its label kernel) at
-                                          an equal byte count: the yardstick already in the tree
+                             concap       vb_concap_finish_batch (csrc/batch.hip: concap_feat_kernel<float, float> of
+                                          csrc/feat_rows.h plus its label kernel) at an equal byte count: the yardstick
+                                          already in the tree
                              dense target vbd_dense_target
                            Both feature kernels rotate through four sets of feature buffers (660 MB, beyond the 256 MiB
                            last-level cache), so their GB/s are figures for memory traffic, not for cache hits.

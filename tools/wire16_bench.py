@@ -1,4 +1,4 @@
-"""What the half-width (float16) feature wire costs and saves (csrc/wire16.hip; include/vilbert_hip_wire.h), against the fp32 path
+"""What the half-width (float16) feature wire costs and saves (csrc/feat_rows.h, batch.hip, task_batch.hip; include/vilbert_hip_wire.h), against the fp32 path
 at the same shapes in the same process:
 
   kernels   device events around back-to-back launches through the C ABI into preallocated outputs, per shape three legs that

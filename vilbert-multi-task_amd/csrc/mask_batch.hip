@@ -19,11 +19,6 @@ __device__ __forceinline__ long long wave_sum_i64(long long v) {
     return v;
 }
 
-// rows * ld fp32 elements whose BYTE offsets stay inside int64 (the kernels form pointers from them)
-inline bool f32_extent_ok(int64_t rows, int64_t ld) {
-    return vb_extent_ok(rows, ld) && (rows <= 0 || rows * ld <= INT64_MAX / 4);
-}
-
 __device__ __forceinline__ float uniform24(uint32_t h) { return (float)(h >> 8) * (1.0f / 16777216.0f); }
 
 // out_input_ids may alias input_ids (a position is read and written by the same lane): no __restrict__ on the id pointers.
@@ -118,7 +113,7 @@ extern "C" int vbi_concap_mask_batch(void* stream, const vbi_mask_args* a) {
     if (!a->input_ids || !a->input_mask || !a->image_mask || !a->overlaps || !a->out_input_ids || !a->lm_label_ids ||
         !a->image_label || !a->masked_label || !a->zero_row)
         return VB_E_BADARG;
-    if (!f32_extent_ok((int64_t)a->batch * a->regions, a->regions)) return VB_E_RANGE;
+    if (!vb_byte_extent_ok((int64_t)a->batch * a->regions, a->regions, 4)) return VB_E_RANGE;
     if (a->batch == 0) return 0;
     hipLaunchKernelGGL(concap_mask_kernel, dim3((unsigned)a->batch), dim3(MB_WAVE), 0, (hipStream_t)stream, *a);
     VB_LAUNCH_CHECK();
@@ -130,7 +125,7 @@ extern "C" int vbi_zero_rows(void* stream, int64_t rows, int32_t n, float* x, in
     if (rows < 0 || n <= 0 || ldx < n || (out != nullptr && ldo < n)) return VB_E_BADARG;
     if (!x || !flags || out == x) return VB_E_BADARG;
     if (n % 4 != 0 || !vb_row32_ok(x, ldx) || (out != nullptr && !vb_row32_ok(out, ldo))) return VB_E_ALIGN;
-    if (!f32_extent_ok(rows, ldx) || (out != nullptr && !f32_extent_ok(rows, ldo))) return VB_E_RANGE;
+    if (!vb_byte_extent_ok(rows, ldx, 4) || (out != nullptr && !vb_byte_extent_ok(rows, ldo, 4))) return VB_E_RANGE;
     if (rows == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)(rows < ZR_MAX_BLOCKS ? rows : ZR_MAX_BLOCKS));

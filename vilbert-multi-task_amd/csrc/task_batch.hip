@@ -3,78 +3,24 @@
 // vqa_dataset.py:275-310 and refer_expression_dataset.py:241-296: float64 zero padding to max_region_num, mask, dense answer
 // target, region IoU target) and the collate stacks the padded samples. Here the regions of all samples travel back to back and
 // one pass writes the padded [B, R, F] block: the packed rows are read once, the output is written once.
-// HBM-bound: 4 F (N + B R) bytes. The numpy restatement tests/task_batch_restatement.py pins every bit of every kernel, so each
-// fp32 operation is an explicit round-to-nearest intrinsic: hipcc would contract a * b + c into an FMA, numpy and torch do not.
-#include "common.h"
-#include "task_rows.h"
-#include "batch_meta.h"
+// HBM-bound: 4 F (N + B R) bytes from fp32 rows. From binary16 rows (include/vilbert_hip_wire.h) a row is widened as it is read
+// and the block is written as fp32 or bf16: 2 F bytes read per packed row, 4 F or 2 F written per output row. The feature kernel
+// and its arithmetic are in feat_rows.h, one body for all three (input, output) kinds. The numpy restatement
+// tests/task_batch_restatement.py pins every bit of every kernel, so each fp32 operation is an explicit round-to-nearest
+// intrinsic: hipcc would contract a * b + c into an FMA, numpy and torch do not.
+#include "feat_rows.h"
 #include "../../include/vilbert_hip_task_inputs.h"
+#include "../../include/vilbert_hip_wire.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int TF_THREADS = 64;          // one wave owns 256 feature columns of one sample: 8 blocks per sample at F = 2048
-constexpr int TF_UNROLL = 8;            // independent 16-byte loads a thread has in flight
+using vbfeat::sample_span;
+
 constexpr int TM_THREADS = 256;
 constexpr unsigned GRID_Y_MAX = 65535;
 constexpr long DT_MAX_BLOCKS = 1L << 20;
-
-__device__ __forceinline__ vbtask::Span sample_span(const vbd_task_batch& a, long b) {
-    return vbtask::span(a.offsets[b], a.offsets[b + 1], a.total_rows, a.mean_rows != nullptr,
-                        a.mean_rows != nullptr ? a.mean_rows[b] : 0, a.max_regions);
-}
-
-// blockIdx.z == 0: the packed rows of a sample, once: row i goes to output row i + 1 while it is kept and into the column sum
-// while i < count; the sum runs in row order, one __fadd_rn per row (np.sum(x, axis=0) of a C-contiguous fp32 array), and is
-// divided in fp32 by (float)count (numpy: float32 array / Python int). The loads of TF_UNROLL rows are issued before the first
-// of them is used; only the adds are serial.
-// blockIdx.z == 1: the zero rows kept_b .. R - 1 (stores only, nothing to wait for).
-__global__ __launch_bounds__(TF_THREADS) void task_feat_kernel(const vbd_task_batch a) {
-    const int F = a.feat_dim;
-    const long c = ((long)blockIdx.x * TF_THREADS + threadIdx.x) * 4;
-    if (c >= F) return;
-    const long R = a.max_regions;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    for (long b = blockIdx.y; b < a.batch; b += gridDim.y) {
-        const vbtask::Span sp = sample_span(a, b);
-        float* dst = a.out_feat + (b * R) * F + c;
-        if (blockIdx.z == 1) {
-            for (long r = sp.kept; r < R; ++r) *reinterpret_cast<f32x4*>(dst + r * F) = zero;
-            continue;
-        }
-        const float* src = a.feat + sp.start * F + c;
-        const long copied = sp.kept - 1;                       // packed rows 0 .. copied - 1 are output rows 1 .. copied
-        const long lim = sp.mean > copied ? sp.mean : copied;  // <= sp.rows: nothing beyond the sample's span is read
-        f32x4 s = zero;
-        for (long i0 = 0; i0 < lim; i0 += TF_UNROLL) {
-            f32x4 v[TF_UNROLL];
-#pragma unroll
-            for (int u = 0; u < TF_UNROLL; ++u) {
-                v[u] = zero;
-                if (i0 + u < lim) v[u] = *reinterpret_cast<const f32x4*>(src + (i0 + u) * F);
-            }
-#pragma unroll
-            for (int u = 0; u < TF_UNROLL; ++u) {
-                const long i = i0 + u;
-                if (i < copied) *reinterpret_cast<f32x4*>(dst + (i + 1) * F) = v[u];
-                if (i < sp.mean) {
-                    s[0] = __fadd_rn(s[0], v[u][0]);
-                    s[1] = __fadd_rn(s[1], v[u][1]);
-                    s[2] = __fadd_rn(s[2], v[u][2]);
-                    s[3] = __fadd_rn(s[3], v[u][3]);
-                }
-            }
-        }
-        f32x4 g = zero;
-        if (sp.mean > 0) {
-            const float n = (float)sp.mean;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) g[e] = __fdiv_rn(s[e], n);
-        }
-        *reinterpret_cast<f32x4*>(dst) = g;
-    }
-}
 
 // the reference's iou() for one anchor against one box (refer_expression_dataset.py:19-56, the + 1 pixel convention)
 __device__ __forceinline__ float iou_px(float ax1, float ay1, float ax2, float ay2, float gx1, float gy1, float gx2, float gy2) {
@@ -88,8 +34,10 @@ __device__ __forceinline__ float iou_px(float ax1, float ay1, float ax2, float a
     return __fdiv_rn(inter, __fsub_rn(__fadd_rn(a_area, g_area), inter));
 }
 
-// One block per sample: boxes, region mask and (optional) the region-IoU target; a thread owns output row r.
-__global__ __launch_bounds__(TM_THREADS) void task_meta_kernel(const vbd_task_batch a) {
+// One block per sample: boxes, region mask and (optional) the region-IoU target; a thread owns output row r. The feature
+// pointers of Args (vbd_task_batch or vbw_task_batch) are not read.
+template <typename Args>
+__global__ __launch_bounds__(TM_THREADS) void task_meta_kernel(const Args a) {
     const long R = a.max_regions;
     for (long b = blockIdx.x; b < a.batch; b += gridDim.x) {
         const vbtask::Span sp = sample_span(a, b);
@@ -147,42 +95,56 @@ __global__ __launch_bounds__(256) void dense_target_kernel(long rows, int num_la
     }
 }
 
-// rows * ld fp32 elements whose BYTE offsets stay inside int64 (the kernels form pointers from them)
-inline bool f32_extent_ok(int64_t rows, int64_t ld) {
-    return vb_extent_ok(rows, ld) && (rows <= 0 || rows * ld <= INT64_MAX / 4);
-}
-
-}  // namespace
-
-int vbmeta::task_meta(hipStream_t st, const vbd_task_batch& a) {
-    hipLaunchKernelGGL(task_meta_kernel, dim3((unsigned)a.batch), dim3(TM_THREADS), 0, st, a);
-    VB_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int vbd_task_finish_batch(void* stream, const vbd_task_batch* a) {
+// What both builders refuse alike (Args: vbd_task_batch or vbw_task_batch; vbfeat::Cols<In> names the input rows): the
+// documented errors of the two calls but out_kind, in their documented order. The output extent is checked for fp32 elements
+// whichever kind is written.
+template <typename In, typename Args>
+int check_args(const Args* a) {
     if (a == nullptr || a->batch < 0 || a->total_rows < 0 || a->max_regions <= 0 || a->feat_dim <= 0) return VB_E_BADARG;
     if (!(a->iou_floor >= 0.f)) return VB_E_BADARG;          // NaN too
     if (!a->feat || !a->boxes || !a->offsets || !a->image_wh || !a->out_feat || !a->out_spatials || !a->out_mask)
         return VB_E_BADARG;
     if ((a->ref_box == nullptr) != (a->out_iou == nullptr)) return VB_E_BADARG;
-    if (a->feat_dim % 4 != 0 || !vb_aligned16(a->feat) || !vb_aligned16(a->out_feat)) return VB_E_ALIGN;
-    if (!f32_extent_ok(a->total_rows, a->feat_dim) || !f32_extent_ok((int64_t)a->batch * a->max_regions, a->feat_dim))
+    if (a->feat_dim % vbfeat::Cols<In>::N != 0 || !vb_aligned16(a->feat) || !vb_aligned16(a->out_feat)) return VB_E_ALIGN;
+    if (!vb_byte_extent_ok(a->total_rows, a->feat_dim, sizeof(In)) ||
+        !vb_byte_extent_ok((int64_t)a->batch * a->max_regions, a->feat_dim, 4))
         return VB_E_RANGE;
-    if (a->batch == 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-    const unsigned by = (unsigned)a->batch < GRID_Y_MAX ? (unsigned)a->batch : GRID_Y_MAX;
-    const dim3 grid((unsigned)((a->feat_dim / 4 + TF_THREADS - 1) / TF_THREADS), by, 2);
-    hipLaunchKernelGGL(task_feat_kernel, grid, dim3(TF_THREADS), 0, st, *a);
+    return 0;
+}
+
+// the feature kernel of (In, Out), then the boxes / mask / IoU target; arguments checked by the callers
+template <typename In, typename Out, typename Args>
+int launch(hipStream_t st, const Args& a) {
+    typedef vbfeat::Cols<In> G;
+    if (a.batch == 0) return 0;
+    const unsigned by = (unsigned)a.batch < GRID_Y_MAX ? (unsigned)a.batch : GRID_Y_MAX;
+    const dim3 grid((unsigned)((a.feat_dim / G::N + G::TASK_THREADS - 1) / G::TASK_THREADS), by, 2);
+    hipLaunchKernelGGL((vbfeat::task_feat_kernel<In, Out, Args>), grid, dim3(G::TASK_THREADS), 0, st, a);
     VB_LAUNCH_CHECK();
-    return vbmeta::task_meta(st, *a);
+    hipLaunchKernelGGL(task_meta_kernel<Args>, dim3((unsigned)a.batch), dim3(TM_THREADS), 0, st, a);
+    VB_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int vbd_task_finish_batch(void* stream, const vbd_task_batch* a) {
+    if (const int e = check_args<float>(a)) return e;
+    return launch<float, float>((hipStream_t)stream, *a);
+}
+
+extern "C" int vbw_task_finish_batch(void* stream, const vbw_task_batch* a) {
+    if (a != nullptr && a->out_kind != VBW_OUT_F32 && a->out_kind != VBW_OUT_BF16) return VB_E_BADARG;
+    if (const int e = check_args<_Float16>(a)) return e;
+    return a->out_kind == VBW_OUT_BF16 ? launch<_Float16, vbfeat::bf16>((hipStream_t)stream, *a)
+                                       : launch<_Float16, float>((hipStream_t)stream, *a);
 }
 
 extern "C" int vbd_dense_target(void* stream, int64_t rows, int32_t num_labels, int32_t K, const int32_t* labels,
                                 const float* scores, float* target, int64_t ldt) {
     if (rows < 0 || num_labels <= 0 || K <= 0 || ldt < num_labels) return VB_E_BADARG;
     if (!labels || !scores || !target) return VB_E_BADARG;
-    if (!f32_extent_ok(rows, ldt) || !f32_extent_ok(rows, K)) return VB_E_RANGE;
+    if (!vb_byte_extent_ok(rows, ldt, 4) || !vb_byte_extent_ok(rows, K, 4)) return VB_E_RANGE;
     if (rows == 0) return 0;
     const int64_t items = rows * (((int64_t)num_labels + 255) / 256);
     hipLaunchKernelGGL(dense_target_kernel, dim3((unsigned)(items < DT_MAX_BLOCKS ? items : DT_MAX_BLOCKS)), dim3(256), 0,

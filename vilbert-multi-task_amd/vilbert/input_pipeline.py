@@ -21,7 +21,7 @@ stream, so the masks of a run differ from the reference's while having the same 
 
 Half-width features (opt-in, ``DeviceBatchPipeline(..., wire_dtype=torch.float16)``): a source that keeps the detector's
 post-ReLU activations (and the region targets) as float16 sends them as they are - half the bytes per step - and the device
-widens them while it finishes the batch (csrc/wire16.hip, ``vbw_concap_finish_batch`` + ``vbw_widen_f16``;
+widens them while it finishes the batch (csrc/batch.hip ``vbw_concap_finish_batch``, csrc/wire16.hip ``vbw_widen_f16``;
 include/vilbert_hip_wire.h). Widening is exact, so the batch holds the bits of the default pipeline fed the widened arrays.
 ``feature_dtype=torch.bfloat16`` writes the feature block as bf16 - what the bf16 stream rounds it to before its first GEMM
 anyway (``BertImageEmbeddings`` takes it as it is) - so the fp32 block and the cast launch are never made. The row clearing of
@@ -29,12 +29,12 @@ the dynamic masking is fused into that pass (``zero_row``): there is no 16-bit r
 never written.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _native as N
+from .staging import StagedPipeline, out_kind
 
 # order of the raw tuple produced by the dataset workers (concept_cap_dataset.py:243-245)
 RAW_FIELDS = ("input_ids", "input_mask", "segment_ids", "lm_label_ids", "is_next", "image_feat", "image_loc",
@@ -181,14 +181,6 @@ def widen_f16(x):
     return y
 
 
-def _out_kind(out_dtype, half, what):
-    if out_dtype not in N.WIRE_OUT_KINDS:
-        raise ValueError("%s: out_dtype must be torch.float32 or torch.bfloat16, got %r" % (what, out_dtype))
-    if out_dtype != torch.float32 and not half:
-        raise ValueError("%s: out_dtype=%s needs float16 features (fp32 features give an fp32 block)" % (what, out_dtype))
-    return N.WIRE_OUT_KINDS[out_dtype]
-
-
 def finish_batch(raw, objective=0, out_dtype=torch.float32):
     """raw: dict of DEVICE tensors named as RAW_FIELDS (worker output, unchanged). Returns the 10-tuple the
     training loop feeds to the model. One native launch pair on the current stream; no torch arithmetic.
@@ -200,7 +192,7 @@ def finish_batch(raw, objective=0, out_dtype=torch.float32):
     if feat.dim() != 3:
         raise RuntimeError("image_feat must be [batch, regions, feat_dim]")
     half = feat.dtype == torch.float16
-    kind = _out_kind(out_dtype, half, "finish_batch")
+    kind = out_kind(out_dtype, half, "finish_batch")
     B, R, F = feat.shape
     T = raw["lm_label_ids"].shape[1]
     dev = feat.device
@@ -252,34 +244,14 @@ def finish_batch(raw, objective=0, out_dtype=torch.float32):
             target, out_ilab, out_mask)
 
 
-class _Slot(object):
-    """One pinned host staging set + its device twin. ``copied``: the H2D copy of the current contents has
-    finished (the host may refill the pinned buffers; compute waits on it). ``released``: the step that read
-    the device buffers has run (the copy stream waits on it before overwriting them)."""
-
-    def __init__(self):
-        self.host, self.dev, self.copied, self.released, self.extra = {}, {}, None, None, ()
-
-    def ensure(self, name, shape, dtype, device):
-        h = self.host.get(name)
-        if h is None or tuple(h.shape) != tuple(shape):
-            self.host[name] = torch.empty(shape, dtype=dtype).pin_memory()
-            self.dev[name] = torch.empty(shape, dtype=dtype, device=device)
-        return self.host[name], self.dev[name]
-
-
-class DeviceBatchPipeline(object):
+class DeviceBatchPipeline(StagedPipeline):
     """Iterate over ``source`` (an iterable of RAW worker batches: tuples of numpy arrays in RAW_FIELDS order,
     optionally followed by extra items such as image ids - what ``self.ds.get_data()`` yields inside the
     reference loader) and yield finished device batches (+ the extra items).
 
     Batch i+1 is staged on a dedicated stream right after the caller has enqueued step i, so the transfer runs
-    under step i. Two staging modes: "direct" (default; the runtime copies straight from the pageable numpy
-    memory) and "pinned" (numpy -> pinned buffer -> asynchronous DMA; on this platform the CPU's writes into
-    the pinned mapping are the slow part).
-    (Staging from a background thread was measured and is slower: the step's ~1500 kernel launches are
-    Python-side work and lose more to GIL hand-offs than the overlap wins - 161 vs 137 ms per step at batch
-    256.) The id / mask / target tensors of a yielded batch alias the slot's device buffers: they stay valid
+    under step i (``StagedPipeline``: the double buffering and the two staging modes, "direct" and "pinned").
+    The id / mask / target tensors of a yielded batch alias the slot's device buffers: they stay valid
     until the caller asks for batch i + depth - 1 (do not keep them across iterations).
 
     masking=None: the source masks (the reference's workers), as above. masking=Masking(...): the source yields UNMASKED
@@ -293,81 +265,22 @@ class DeviceBatchPipeline(object):
     pipeline fed the widened arrays. feature_dtype=torch.bfloat16 (with the float16 wire only) yields image_feat rounded to
     bf16, for the bf16 stream."""
 
+    dtypes, wire_fields, blank_fields = _DTYPES, WIRE_FIELDS, ()
+
     def __init__(self, source, device, objective=0, depth=2, staging=None, masking=None, wire_dtype=None,
                  feature_dtype=torch.float32):
-        self.source, self.device, self.objective = source, torch.device(device), int(objective)
-        self.masking = masking
-        if wire_dtype not in (None, torch.float16):
-            raise ValueError("wire_dtype must be None or torch.float16, got %r" % (wire_dtype,))
-        _out_kind(feature_dtype, wire_dtype is not None, "DeviceBatchPipeline")
-        self.wire_dtype, self.feature_dtype = wire_dtype, feature_dtype
+        StagedPipeline.__init__(self, source, device, depth, staging, wire_dtype, feature_dtype)
+        self.objective, self.masking = int(objective), masking
         self.fields = RAW_FIELDS if masking is None else RAW_UNMASKED_FIELDS
-        self._copy_stream = None
-        self.slots = [_Slot() for _ in range(max(2, depth))]
-        # "pinned": numpy -> pinned host buffer -> asynchronous DMA.  "direct": hand the pageable numpy memory to
-        # the runtime's own copy path (it stages through its internal pinned chunks; blocks the host for the
-        # duration of the transfer but never makes the CPU write through an uncached host mapping).
-        self.staging = staging or os.environ.get("VB_PIPE_STAGING", "direct")   # measured: 131 vs 137-154 ms / step
+        if masking is not None:
+            # all -1 from an unmasked source and never read: mask_batch writes every element of the device buffers
+            self.blank_fields = ("lm_label_ids", "image_label")
 
-    @property
-    def copy_stream(self):
-        if self._copy_stream is None:                       # made on first use: the constructor touches no device
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-        return self._copy_stream
+    def arrays(self, batch):
+        return dict(zip(self.fields, batch)), tuple(batch[len(self.fields):])
 
-    def _dtype(self, name):
-        return self.wire_dtype if self.wire_dtype is not None and name in WIRE_FIELDS else _DTYPES[name]
-
-    def _stage(self, slot, batch):
-        fields = dict(zip(self.fields, batch[:len(self.fields)]))
-        if self.wire_dtype is not None:
-            for name in WIRE_FIELDS:
-                if np.asarray(fields[name]).dtype != np.float16:
-                    raise ValueError("%s: wire_dtype=torch.float16 takes float16 arrays from the source, got %s (the pipeline "
-                                     "never narrows)" % (name, np.asarray(fields[name]).dtype))
-        if slot.copied is not None:
-            slot.copied.synchronize()                       # pinned buffers free again (long done)
-        if slot.released is not None:
-            self.copy_stream.wait_event(slot.released)      # device buffers free once that step has run
-        slot.extra = tuple(batch[len(self.fields):])
-        with torch.cuda.stream(self.copy_stream):
-            for name in self.fields:
-                if self.masking is not None and name in ("lm_label_ids", "image_label"):
-                    # all -1 from an unmasked source and never read: mask_batch writes every element of the device buffer
-                    slot.ensure(name, np.shape(fields[name]), _DTYPES[name], self.device)
-                    continue
-                arr = np.ascontiguousarray(fields[name])
-                h, d = slot.ensure(name, arr.shape, self._dtype(name), self.device)
-                if self.staging == "direct" and arr.dtype == h.numpy().dtype:
-                    d.copy_(torch.from_numpy(arr), non_blocking=False)
-                else:
-                    h.copy_(torch.from_numpy(arr))          # dtype conversion (e.g. int32 ids) happens here
-                    d.copy_(h, non_blocking=True)
-            slot.copied = torch.cuda.Event()
-            slot.copied.record(self.copy_stream)
-
-    def __iter__(self):
-        it = iter(self.source)
-        batch = next(it, None)
-        if batch is None:
-            return
-        idx = 0
-        self._stage(self.slots[0], batch)
-        while True:
-            slot = self.slots[idx]
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(slot.copied)
-            for t in slot.dev.values():
-                t.record_stream(cur)      # allocated on the copy stream, read by kernels of the compute stream
-            raw, m = slot.dev, self.masking
-            if m is not None:
-                raw = mask_batch(raw, m.next_seed(), m.vocab_size, m.mask_token_id, m.p_select, inplace=True)
-            out = finish_batch(raw, self.objective, self.feature_dtype)
-            yield out + slot.extra
-            slot.released = torch.cuda.Event()
-            slot.released.record(torch.cuda.current_stream(self.device))   # after the caller's step
-            batch = next(it, None)
-            if batch is None:
-                return
-            idx = (idx + 1) % len(self.slots)
-            self._stage(self.slots[idx], batch)
+    def finish(self, slot):
+        raw, m = slot.views, self.masking
+        if m is not None:
+            raw = mask_batch(raw, m.next_seed(), m.vocab_size, m.mask_token_id, m.p_select, inplace=True)
+        return finish_batch(raw, self.objective, self.feature_dtype) + slot.extra

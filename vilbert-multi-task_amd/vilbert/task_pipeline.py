@@ -14,17 +14,16 @@ held bit for bit to the reference's own). ``TaskBatchPipeline`` yields the tuple
 
 Half-width features (opt-in): ``pack_task_samples(..., dtype=np.float16)`` packs float16 region features,
 ``TaskBatchPipeline(..., wire_dtype=torch.float16)`` sends them as they are and the device widens them while it builds the batch
-(csrc/wire16.hip, ``vbw_task_finish_batch``; include/vilbert_hip_wire.h) - the bits of the default builder on the widened
+(csrc/task_batch.hip, ``vbw_task_finish_batch``; include/vilbert_hip_wire.h) - the bits of the default builder on the widened
 arrays, or with ``feature_dtype=torch.bfloat16`` those bits rounded to bf16 for the bf16 stream.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _native as N
-from .input_pipeline import _Slot, _out_kind
+from .staging import StagedPipeline, out_kind
 
 PACKED_FIELDS = ("feat", "boxes", "offsets", "image_wh", "mean_rows")
 TOKEN_FIELDS = ("question", "input_mask", "segment_ids")
@@ -105,7 +104,7 @@ def finish_task_batch(packed_dev, max_regions, ref_box=None, iou_floor=0.0, out_
         raise RuntimeError("feat must be [rows, feat_dim] and offsets [batch + 1]")
     (n, F), B, R, dev = feat.shape, offsets.shape[0] - 1, int(max_regions), feat.device
     half = feat.dtype == torch.float16
-    kind = _out_kind(out_dtype, half, "finish_task_batch")
+    kind = out_kind(out_dtype, half, "finish_task_batch")
     a = N.WireTaskBatch() if half else N.TaskBatchArgs()
     a.batch, a.max_regions, a.feat_dim, a.iou_floor, a.total_rows = B, R, F, float(iou_floor), n
     if half:
@@ -147,7 +146,7 @@ def dense_target(labels, scores, num_labels):
     return out
 
 
-class TaskBatchPipeline(object):
+class TaskBatchPipeline(StagedPipeline):
     """Iterate over ``source`` - an iterable of batches, each a dict of numpy arrays: the five arrays of
     ``pack_task_samples``, the token arrays ``question``, ``input_mask``, ``segment_ids`` [B, T], ``question_id`` [B] and what
     the target needs - and yield finished device batches in the reference datasets' tuple order
@@ -157,8 +156,8 @@ class TaskBatchPipeline(object):
     target=("dense", L)       ``labels`` / ``scores`` [B, K] (int32 padded with -1 / fp32) become the dense [B, L] target
     target=("iou", floor)     ``ref_box`` [B, 4] (pixel x1, y1, x2, y2) becomes the region-IoU target [B, R, 1]
 
-    Batch i + 1 is staged on a dedicated stream right after the caller has enqueued step i (double buffered, the two staging
-    modes of ``DeviceBatchPipeline``). The packed arrays change length from batch to batch: a slot's buffers are sized by
+    Batch i + 1 is staged on a dedicated stream right after the caller has enqueued step i (``StagedPipeline``: double
+    buffered, two staging modes). The packed arrays change length from batch to batch: a slot's buffers are sized by
     CAPACITY (first dimension, grow only) and a batch uses a leading view of them. The token tensors are copied as they are
     and alias the slot's device buffers: they stay valid until the caller asks for batch i + depth - 1. co_attention_mask
     is one cached zero tensor [B, R, T] (the reference builds a fresh one per sample; nothing writes to it).
@@ -168,66 +167,22 @@ class TaskBatchPipeline(object):
     default pipeline fed the widened array. feature_dtype=torch.bfloat16 (with the float16 wire only) yields the features
     rounded to bf16."""
 
+    dtypes, wire_fields = _DTYPES, ("feat",)
+
     def __init__(self, source, device, max_regions, target=None, depth=2, staging=None, wire_dtype=None,
                  feature_dtype=torch.float32):
-        self.source, self.device, self.max_regions = source, torch.device(device), int(max_regions)
-        if wire_dtype not in (None, torch.float16):
-            raise ValueError("wire_dtype must be None or torch.float16, got %r" % (wire_dtype,))
-        _out_kind(feature_dtype, wire_dtype is not None, "TaskBatchPipeline")
-        self.wire_dtype, self.feature_dtype = wire_dtype, feature_dtype
+        StagedPipeline.__init__(self, source, device, depth, staging, wire_dtype, feature_dtype)
+        self.max_regions = int(max_regions)
         if target is not None and (len(target) != 2 or target[0] not in ("dense", "iou")):
             raise ValueError("target must be None, ('dense', num_labels) or ('iou', floor), got %r" % (target,))
         self.target = target
+        # a target the source supplies keeps its own dtype (int64 labels for cross-entropy, fp32 soft labels)
         extra = {None: ("target",), "dense": ("labels", "scores"), "iou": ("ref_box",)}[target[0] if target else None]
         self.fields = PACKED_FIELDS + TOKEN_FIELDS + ("question_id",) + extra
-        self._copy_stream = None
-        self.slots = [_Slot() for _ in range(max(2, depth))]
-        self.staging = staging or os.environ.get("VB_PIPE_STAGING", "direct")
         self._co_attention = {}
 
-    @property
-    def copy_stream(self):
-        if self._copy_stream is None:                       # made on first use: the constructor touches no device
-            self._copy_stream = torch.cuda.Stream(device=self.device)
-        return self._copy_stream
-
-    def _ensure(self, slot, name, shape, dtype):
-        """Leading views [shape[0]] of the slot's host / device buffers of `name`, reallocated only when the batch does not
-        fit (more rows than ever before, or other trailing dimensions)."""
-        d = slot.dev.get(name)
-        if d is None or d.dtype != dtype or tuple(d.shape[1:]) != tuple(shape[1:]) or d.shape[0] < shape[0]:
-            cap = (max(int(shape[0]), 1),) + tuple(shape[1:])
-            slot.dev[name] = d = torch.empty(cap, dtype=dtype, device=self.device)
-            if self.staging != "direct":                    # "direct" copies from the numpy memory: no host twin
-                slot.host[name] = torch.empty(cap, dtype=dtype).pin_memory()
-        h = slot.host.get(name)
-        return (None if h is None else h[:shape[0]]), d[:shape[0]]
-
-    def _stage(self, slot, batch):
-        if self.wire_dtype is not None and np.asarray(batch["feat"]).dtype != np.float16:
-            raise ValueError("feat: wire_dtype=torch.float16 takes a float16 array from the source, got %s (the pipeline never "
-                             "narrows)" % np.asarray(batch["feat"]).dtype)
-        if slot.copied is not None:
-            slot.copied.synchronize()                       # pinned buffers free again (long done)
-        if slot.released is not None:
-            self.copy_stream.wait_event(slot.released)      # device buffers free once that step has run
-        views = {}
-        with torch.cuda.stream(self.copy_stream):
-            for name in self.fields:
-                arr = np.ascontiguousarray(batch[name])
-                src = torch.from_numpy(arr)
-                # a target the source supplies keeps its own dtype (int64 labels for cross-entropy, fp32 soft labels)
-                dtype = self.wire_dtype if name == "feat" and self.wire_dtype is not None else _DTYPES.get(name, src.dtype)
-                h, d = self._ensure(slot, name, arr.shape, dtype)
-                if h is None:
-                    d.copy_(src, non_blocking=False)        # "direct": dtype conversion, if any, is the runtime's
-                else:
-                    h.copy_(src)
-                    d.copy_(h, non_blocking=True)
-                views[name] = d
-            slot.copied = torch.cuda.Event()
-            slot.copied.record(self.copy_stream)
-        slot.extra = views
+    def arrays(self, batch):
+        return batch, ()
 
     def _zeros(self, B, T):
         t = self._co_attention.get((B, T))
@@ -235,34 +190,15 @@ class TaskBatchPipeline(object):
             t = self._co_attention[(B, T)] = torch.zeros(B, self.max_regions, T, dtype=torch.float32, device=self.device)
         return t
 
-    def __iter__(self):
-        it = iter(self.source)
-        batch = next(it, None)
-        if batch is None:
-            return
-        idx = 0
-        self._stage(self.slots[0], batch)
-        while True:
-            slot = self.slots[idx]
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(slot.copied)
-            for name in self.fields:
-                slot.dev[name].record_stream(cur)     # allocated on the copy stream, read by kernels of the compute stream
-            v = slot.extra
-            kind = self.target[0] if self.target else None
-            out = finish_task_batch(v, self.max_regions, ref_box=v["ref_box"] if kind == "iou" else None,
-                                    iou_floor=float(self.target[1]) if kind == "iou" else 0.0, out_dtype=self.feature_dtype)
-            if kind == "dense":
-                target = dense_target(v["labels"], v["scores"], int(self.target[1]))
-            else:
-                target = out[3] if kind == "iou" else v["target"]
-            B, T = v["question"].shape
-            yield (out[0], out[1], out[2], v["question"], target, v["input_mask"], v["segment_ids"], self._zeros(B, T),
-                   v["question_id"])
-            slot.released = torch.cuda.Event()
-            slot.released.record(torch.cuda.current_stream(self.device))   # after the caller's step
-            batch = next(it, None)
-            if batch is None:
-                return
-            idx = (idx + 1) % len(self.slots)
-            self._stage(self.slots[idx], batch)
+    def finish(self, slot):
+        v = slot.views
+        kind = self.target[0] if self.target else None
+        out = finish_task_batch(v, self.max_regions, ref_box=v["ref_box"] if kind == "iou" else None,
+                                iou_floor=float(self.target[1]) if kind == "iou" else 0.0, out_dtype=self.feature_dtype)
+        if kind == "dense":
+            target = dense_target(v["labels"], v["scores"], int(self.target[1]))
+        else:
+            target = out[3] if kind == "iou" else v["target"]
+        B, T = v["question"].shape
+        return (out[0], out[1], out[2], v["question"], target, v["input_mask"], v["segment_ids"], self._zeros(B, T),
+                v["question_id"])
