@@ -118,14 +118,28 @@ __global__ __launch_bounds__(Cols<In>::CONCAP_THREADS) void concap_feat_kernel(i
     }
 }
 
-// the clamped span of sample b of a packed fine-tuning batch (Args: vbd_task_batch or vbw_task_batch)
+// Where the rows of output sample b come from, per argument struct. image(a, b): the index of the sample's per-image words
+// (image_wh, mean_rows), or < 0 for a sample that owns nothing - such a sample reads none of them; span(a, img): its clamped
+// rows. The per-batch words (ref_box, the outputs) are always indexed by b.
+// This one: a packed fine-tuning batch (vbd_task_batch or vbw_task_batch), whose sample b is image b. region_store.hip
+// specialises it for a device-resident store, whose samples name their image by an id word.
+template <typename Args>
+struct Source {
+    static __device__ __forceinline__ long image(const Args&, long b) { return b; }
+    static __device__ __forceinline__ vbtask::Span span(const Args& a, long img) {
+        return vbtask::span(a.offsets[img], a.offsets[img + 1], a.total_rows, a.mean_rows != nullptr,
+                            a.mean_rows != nullptr ? a.mean_rows[img] : 0, a.max_regions);
+    }
+};
+
+// the clamped span of output sample b
 template <typename Args>
 __device__ __forceinline__ vbtask::Span sample_span(const Args& a, long b) {
-    return vbtask::span(a.offsets[b], a.offsets[b + 1], a.total_rows, a.mean_rows != nullptr,
-                        a.mean_rows != nullptr ? a.mean_rows[b] : 0, a.max_regions);
+    return Source<Args>::span(a, Source<Args>::image(a, b));
 }
 
-// Fine-tuning builder; of Args only the fields vbd_task_batch and vbw_task_batch share are read (feat / out_feat by address).
+// Fine-tuning builder; of Args only the fields vbd_task_batch, vbw_task_batch and vbr_store_batch share are read (feat /
+// out_feat by address), the sample's rows only through sample_span. A sample that owns nothing (kept == 0) is zeros, row 0 too.
 // blockIdx.z == 0: the packed rows of a sample, once: row i goes to output row i + 1 while it is kept and into the column sum
 // while i < count; the sum runs in row order, one __fadd_rn per row (np.sum(x, axis=0) of a C-contiguous fp32 array), and is
 // divided in fp32 by (float)count (numpy: float32 array / Python int); count == 0: zeros.

@@ -5,10 +5,11 @@
 // one pass writes the padded [B, R, F] block: the packed rows are read once, the output is written once.
 // HBM-bound: 4 F (N + B R) bytes from fp32 rows. From binary16 rows (include/vilbert_hip_wire.h) a row is widened as it is read
 // and the block is written as fp32 or bf16: 2 F bytes read per packed row, 4 F or 2 F written per output row. The feature kernel
-// and its arithmetic are in feat_rows.h, one body for all three (input, output) kinds. The numpy restatement
+// and its arithmetic are in feat_rows.h, one body for all three (input, output) kinds; the boxes / mask / IoU-target kernel and
+// the launch pair are in task_meta.h, shared with the device-resident store (region_store.hip). The numpy restatement
 // tests/task_batch_restatement.py pins every bit of every kernel, so each fp32 operation is an explicit round-to-nearest
 // intrinsic: hipcc would contract a * b + c into an FMA, numpy and torch do not.
-#include "feat_rows.h"
+#include "task_meta.h"
 #include "../../include/vilbert_hip_task_inputs.h"
 #include "../../include/vilbert_hip_wire.h"
 
@@ -16,65 +17,9 @@
 
 namespace {
 
-using vbfeat::sample_span;
+using vbmeta::launch;
 
-constexpr int TM_THREADS = 256;
-constexpr unsigned GRID_Y_MAX = 65535;
 constexpr long DT_MAX_BLOCKS = 1L << 20;
-
-// the reference's iou() for one anchor against one box (refer_expression_dataset.py:19-56, the + 1 pixel convention)
-__device__ __forceinline__ float iou_px(float ax1, float ay1, float ax2, float ay2, float gx1, float gy1, float gx2, float gy2) {
-    const float g_area = __fmul_rn(__fadd_rn(__fsub_rn(gx2, gx1), 1.f), __fadd_rn(__fsub_rn(gy2, gy1), 1.f));
-    const float a_area = __fmul_rn(__fadd_rn(__fsub_rn(ax2, ax1), 1.f), __fadd_rn(__fsub_rn(ay2, ay1), 1.f));
-    float iw = __fadd_rn(__fsub_rn(fminf(ax2, gx2), fmaxf(ax1, gx1)), 1.f);
-    float ih = __fadd_rn(__fsub_rn(fminf(ay2, gy2), fmaxf(ay1, gy1)), 1.f);
-    if (iw < 0.f) iw = 0.f;
-    if (ih < 0.f) ih = 0.f;
-    const float inter = __fmul_rn(iw, ih);
-    return __fdiv_rn(inter, __fsub_rn(__fadd_rn(a_area, g_area), inter));
-}
-
-// One block per sample: boxes, region mask and (optional) the region-IoU target; a thread owns output row r. The feature
-// pointers of Args (vbd_task_batch or vbw_task_batch) are not read.
-template <typename Args>
-__global__ __launch_bounds__(TM_THREADS) void task_meta_kernel(const Args a) {
-    const long R = a.max_regions;
-    for (long b = blockIdx.x; b < a.batch; b += gridDim.x) {
-        const vbtask::Span sp = sample_span(a, b);
-        const int32_t W = a.image_wh[2 * b], H = a.image_wh[2 * b + 1];
-        const float w = (float)W, h = (float)H, wh = (float)((int64_t)W * (int64_t)H);
-        float gx1 = 0.f, gy1 = 0.f, gx2 = 0.f, gy2 = 0.f;
-        if (a.ref_box != nullptr) {
-            gx1 = a.ref_box[4 * b]; gy1 = a.ref_box[4 * b + 1]; gx2 = a.ref_box[4 * b + 2]; gy2 = a.ref_box[4 * b + 3];
-        }
-        for (long r = threadIdx.x; r < R; r += TM_THREADS) {
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, t = 0.f;
-            const bool kept = r < sp.kept;
-            if (kept) {
-                float x1 = 0.f, y1 = 0.f, x2 = w, y2 = h;          // the global row's pixel box
-                if (r == 0) {
-                    s2 = 1.f; s3 = 1.f; s4 = 1.f;
-                } else {
-                    const float* box = a.boxes + (sp.start + r - 1) * 4;
-                    x1 = box[0]; y1 = box[1]; x2 = box[2]; y2 = box[3];
-                    s0 = __fdiv_rn(x1, w);
-                    s1 = __fdiv_rn(y1, h);
-                    s2 = __fdiv_rn(x2, w);
-                    s3 = __fdiv_rn(y2, h);
-                    s4 = __fdiv_rn(__fmul_rn(__fsub_rn(y2, y1), __fsub_rn(x2, x1)), wh);
-                }
-                if (a.out_iou != nullptr) {
-                    t = iou_px(x1, y1, x2, y2, gx1, gy1, gx2, gy2);
-                    if (t < a.iou_floor) t = 0.f;
-                }
-            }
-            float* sp_out = a.out_spatials + (b * R + r) * 5;
-            sp_out[0] = s0; sp_out[1] = s1; sp_out[2] = s2; sp_out[3] = s3; sp_out[4] = s4;
-            a.out_mask[b * R + r] = kept ? 1 : 0;
-            if (a.out_iou != nullptr) a.out_iou[b * R + r] = t;
-        }
-    }
-}
 
 // One block per (row, 256-column chunk), grid-strided; a thread owns one column and scans the K labels of its row in order, so
 // the LAST matching k wins. The labels and scores of a row are block-uniform reads that stay in cache.
@@ -109,20 +54,6 @@ int check_args(const Args* a) {
     if (!vb_byte_extent_ok(a->total_rows, a->feat_dim, sizeof(In)) ||
         !vb_byte_extent_ok((int64_t)a->batch * a->max_regions, a->feat_dim, 4))
         return VB_E_RANGE;
-    return 0;
-}
-
-// the feature kernel of (In, Out), then the boxes / mask / IoU target; arguments checked by the callers
-template <typename In, typename Out, typename Args>
-int launch(hipStream_t st, const Args& a) {
-    typedef vbfeat::Cols<In> G;
-    if (a.batch == 0) return 0;
-    const unsigned by = (unsigned)a.batch < GRID_Y_MAX ? (unsigned)a.batch : GRID_Y_MAX;
-    const dim3 grid((unsigned)((a.feat_dim / G::N + G::TASK_THREADS - 1) / G::TASK_THREADS), by, 2);
-    hipLaunchKernelGGL((vbfeat::task_feat_kernel<In, Out, Args>), grid, dim3(G::TASK_THREADS), 0, st, a);
-    VB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(task_meta_kernel<Args>, dim3((unsigned)a.batch), dim3(TM_THREADS), 0, st, a);
-    VB_LAUNCH_CHECK();
     return 0;
 }
 

@@ -127,10 +127,15 @@ _install_optimization_finder()
 # `from vilbert import TaskBatchPipeline` (vilbert/task_pipeline.py). Resolved on first use: importing the package loads
 # neither torch nor the native library.
 _TASK_PIPELINE_NAMES = ("raw_item", "pack_task_samples", "finish_task_batch", "dense_target", "TaskBatchPipeline")
+# `from vilbert import RegionStore` (vilbert/region_store.py): the device-resident region store and its pipeline
+_REGION_STORE_NAMES = ("RegionStore", "StoreBatchPipeline")
 
 
 def __getattr__(name):
     if name in _TASK_PIPELINE_NAMES:
         from . import task_pipeline
         return getattr(task_pipeline, name)
+    if name in _REGION_STORE_NAMES:
+        from . import region_store
+        return getattr(region_store, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

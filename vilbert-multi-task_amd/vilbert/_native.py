@@ -339,6 +339,21 @@ class WireTaskBatch(ctypes.Structure):
     ]
 
 
+class StoreBatchArgs(ctypes.Structure):
+    """vbr_store_batch (128 bytes; include/vilbert_hip_store.h)"""
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("max_regions", ctypes.c_int32), ("feat_dim", ctypes.c_int32),
+        ("iou_floor", ctypes.c_float),
+        ("feat_kind", ctypes.c_int32), ("out_kind", ctypes.c_int32),
+        ("total_rows", ctypes.c_int64), ("num_images", ctypes.c_int64),
+        ("feat", ctypes.c_void_p), ("boxes", ctypes.c_void_p), ("image_offsets", ctypes.c_void_p),
+        ("image_wh", ctypes.c_void_p), ("mean_rows", ctypes.c_void_p), ("image_ids", ctypes.c_void_p),
+        ("ref_box", ctypes.c_void_p),
+        ("out_feat", ctypes.c_void_p), ("out_spatials", ctypes.c_void_p), ("out_mask", ctypes.c_void_p),
+        ("out_iou", ctypes.c_void_p),
+    ]
+
+
 class ConcapBatch(ctypes.Structure):
     """vb_concap_batch"""
     _fields_ = [
@@ -517,6 +532,13 @@ WIRE_SIGNATURES = {
 }
 WIRE_OUT_KINDS = {torch.float32: 0, torch.bfloat16: 1}
 
+# include/vilbert_hip_store.h (fine-tuning batches gathered from a device-resident region store by image index; prefix vbr_),
+# mirrored one to one (checked by tests/test_region_store.py)
+STORE_SIGNATURES = {
+    "vbr_store_finish_batch": (ctypes.c_int, [_P, ctypes.POINTER(StoreBatchArgs)]),
+}
+STORE_FEAT_KINDS = {torch.float32: 0, torch.float16: 1}       # VBR_FEAT_*; VBR_OUT_* are the words of WIRE_OUT_KINDS
+
 _lib = None
 
 
@@ -534,7 +556,7 @@ def lib():
                                   + list(HEADS_SIGNATURES.items()) + list(FINETUNE_SIGNATURES.items())
                                   + list(LAMB_SIGNATURES.items()) + list(INPUT_SIGNATURES.items())
                                   + list(TASK_INPUT_SIGNATURES.items()) + list(BASELINE_SIGNATURES.items())
-                                  + list(WIRE_SIGNATURES.items())):
+                                  + list(WIRE_SIGNATURES.items()) + list(STORE_SIGNATURES.items())):
             fn = getattr(handle, name)  # AttributeError if the .so is stale
             fn.restype, fn.argtypes = res, args
         if handle.vb_abi_version() != 18:
